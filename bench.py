@@ -14,6 +14,13 @@ Prints ONE JSON line (rank 0).  value = audio seconds transcribed per wall secon
 over all ranks (max-over-ranks time).  Weights are random (no checkpoint is
 available offline) and decoding runs to <|endoftext|> or max_length, so tokens
 per clip are reported beside the number.
+
+A plain run does only what that headline needs: set up, warm up, the timed steps, the
+line.  ``--full`` adds every other leg to the line (realistic lengths, beam 5, the
+roofline pass, batch-1 latency, the streaming and REST simulations, ingest, the CPU
+baseline); the options that size those legs only matter with it.  ``--dump-outputs DIR``
+writes what the last timed step returned as ``DIR/<name>.npy`` (inputs and weights are
+seeded, so two builds can be compared output for output).
 """
 from __future__ import annotations
 
@@ -53,6 +60,11 @@ LENGTH_CONTROL_TPS = 4.0
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (realistic lengths, beam 5, roofline pass, batch-1 "
+                         "latency, streaming, REST, ingest, CPU baseline); the options below that size them need it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's outputs as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--steps", type=int, default=20,
                     help="timed 64-clip steps; the first ~3 fill the lanes' pipeline (measured, r03_ac: "
                          "6 steps 4942, 12 steps 5043, 24 steps 5099 audio-s/s)")
@@ -124,6 +136,7 @@ class StandInEngine:
     def transcribe_batch(self, clips, cfg, device_pcm=None, offsets=None):
         class _Out:
             tokens = list(range(self.rank + 1))
+            sum_logprob, no_speech_prob, language = 0.0, 0.0, 0
         time.sleep(0.04 * (self.rank + 1))
         return [_Out() for _ in clips]
 
@@ -402,11 +415,32 @@ def timed_steps(dp, allpcm, k: int, dist=None, dev=None, runner=None):
     return el, ntok, res
 
 
+def dump_outputs(path: str, outs, ids, ctx: int) -> None:
+    """--dump-outputs: what the last timed step handed its caller, one float32 array per
+    file (token ids <= 51865 are exact in float32).  `ids` are the gathered token ids of
+    every clip of the step in global clip order, `outs` rank 0's own WindowOutputs.
+      tokens.npy          [clips, ctx]  ids, -1 after a clip's last token
+      n_tokens.npy        [clips]
+      sum_logprob.npy, no_speech_prob.npy, language.npy   [rank 0's clips]
+    64 clips x 448 positions: 115 kB per rank."""
+    os.makedirs(path, exist_ok=True)
+    tok = np.full((len(ids), ctx), -1.0, np.float32)
+    for i, t in enumerate(ids):
+        tok[i, :len(t)] = t[:ctx]
+    arrays = {"tokens": tok, "n_tokens": [len(t) for t in ids],
+              "sum_logprob": [o.sum_logprob for o in outs], "no_speech_prob": [o.no_speech_prob for o in outs],
+              "language": [o.language for o in outs]}
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(arr, dtype=np.float32))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     a = parse(argv)
     if a.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if a.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and a.gpus > 1:
         # one process per GPU: start the ranks ourselves (nothing here has touched the GPU)
@@ -453,6 +487,8 @@ def main(argv=None):
     # warm-up: every lane captures its decode graph
     dp.run_steps(allpcm, max(a.warmup, len(dp.lanes)) if a.warmup > 0 else 0)
     el, ntok, res = timed_steps(dp, allpcm, a.steps, dist, dev)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, res[-1][0], res[-1][1], dims.n_text_ctx)
 
     audio_s = n_total * a.steps * 30.0
     value = audio_s / el
@@ -481,7 +517,7 @@ def main(argv=None):
     # the next queued clip, so a lane's rows stay full across its steps instead of every
     # batch waiting for its longest window.  The plain per-batch path is timed beside it.
     realistic = None
-    if a.realistic_steps > 0:
+    if a.full and a.realistic_steps > 0:
         lens = np.clip(np.round(np.random.default_rng(77).normal(130, 40, B)), 16, 440).astype(int)
         import dataclasses
         dp.cfg = dataclasses.replace(cfg, token_budget=tuple(int(x) for x in lens))
@@ -505,7 +541,7 @@ def main(argv=None):
     # The reference's own decoding (beam_size=5, src/backends/faster_whisper.py:237) on the
     # same lanes: warm-up steps let every lane capture its beam graph, then K_b timed steps.
     beam5_lanes = None
-    if a.beam5_steps > 0:
+    if a.full and a.beam5_steps > 0:
         dp.cfg = DecodeConfig(suppress_tokens=sup, max_length=a.max_length, beam_size=5)
         dp.run_steps(allpcm, len(dp.lanes))
         bel, btok_all, _ = timed_steps(dp, allpcm, a.beam5_steps, dist, dev)
@@ -515,7 +551,8 @@ def main(argv=None):
                        "lanes_per_gpu": len(dp.lanes), "tokens_per_clip": round(btok, 1)}
         dp.cfg = cfg
 
-    if rank == 0:
+    extras = {}
+    if rank == 0 and a.full:
         # Roofline pass, after the timed region: lane 0 alone runs one more step of the
         # same workload with per-kernel HIP-event timers on its stream and the decode
         # steps launched eagerly (inside the timed region the lanes overlap, so a
@@ -620,6 +657,23 @@ def main(argv=None):
         if not a.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(dims, tokens_per_clip, a.cpu_decode_steps)
 
+        extras = {
+            "p50_latency_ms_b1": p50,
+            "latency_b1": {"greedy": lat_greedy, "beam5": lat_beam},
+            "beam5": beam5_lanes,
+            "realistic_lengths": realistic,
+            "streaming": stream,
+            "rest_mixed": rest,
+            "ingest": ingest_t,
+            "beam5_audio_sec_per_sec_1lane": beam5,
+            "roofline": roof,
+            "rooflines": {k: {kk: v[kk] for kk in ("achieved", "unit", "frac", "avg_launch_ms", "valu") if kk in v}
+                          for k, v in roofs.items()},
+            "stages_ms_roofline_pass": stages,
+            "cpu_baseline": cpu,
+        }
+
+    if rank == 0:
         line = {
             "metric": "audio-sec/sec (whisper-large-v3-turbo, 30 s clips, greedy)",
             "value": round(value, 2), "unit": "audio-sec/sec", "n_gpus": world, "steps": a.steps,
@@ -630,22 +684,11 @@ def main(argv=None):
                        "clips_per_gpu": B, "global_batch": n_total, "parallelism": f"dp{world}",
                        "lanes_per_gpu": len(dp.lanes)},
             "tokens_per_clip": round(tokens_per_clip, 1),
-            "p50_latency_ms_b1": p50,
-            "latency_b1": {"greedy": lat_greedy, "beam5": lat_beam},
-            "beam5": beam5_lanes,
-            "realistic_lengths": realistic,
-            "streaming": stream,
-            "rest_mixed": rest,
-            "ingest": ingest_t,
-            "beam5_audio_sec_per_sec_1lane": beam5,
             "realtime_factor": round(value, 1),
-            "roofline": roof,
-            "rooflines": {k: {kk: v[kk] for kk in ("achieved", "unit", "frac", "avg_launch_ms", "valu") if kk in v}
-                          for k, v in roofs.items()},
-            "stages_ms_roofline_pass": stages,
             "decode_steps_last_call": int(profs[0]["decode_steps"]),
-            "cpu_baseline": cpu,
+            "full": bool(a.full),
         }
+        line.update(extras)
         print(json.dumps(line), flush=True)
     dp.close()
     eng.close()

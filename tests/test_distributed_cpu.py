@@ -199,3 +199,22 @@ def test_bench_accounting_gloo():
     assert el0 >= 4 * 0.04 * 2             # at least the slow rank's 4 steps x 80 ms
     assert n0 == n1 == 4 * 3 * (1 + 2)     # tokens summed over both ranks
     assert k0 == k1 == 4
+
+
+def test_bench_dump_outputs_standin(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's outputs as float32 .npy files: the
+    token ids of every clip (-1 after a clip's last token), their counts and the per-clip
+    scalars.  A plain run's line carries the headline fields and none of the --full legs."""
+    import numpy as np
+    out = tmp_path / "dump"
+    p, lines = _run_bench(["--gpus", "1", "--standin", "--batch", "3", "--steps", "2", "--warmup", "1",
+                           "--dump-outputs", str(out)])
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert len(lines) == 1 and lines[0]["steps"] == 2 and lines[0]["ms_per_step"] >= 40.0
+    got = {f.name: np.load(f) for f in out.iterdir()}
+    assert sorted(got) == ["language.npy", "n_tokens.npy", "no_speech_prob.npy", "sum_logprob.npy", "tokens.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["tokens.npy"].shape == (3, 448)
+    assert (got["tokens.npy"][:, 0] == 0).all() and (got["tokens.npy"][:, 1:] == -1).all()   # rank 0: one token, id 0
+    assert got["n_tokens.npy"].tolist() == [1.0, 1.0, 1.0]
+    assert got["sum_logprob.npy"].shape == (3,)

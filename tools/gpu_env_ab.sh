@@ -3,7 +3,7 @@
 set -e
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/$1; shift; mkdir -p $O
-ARGS=${BENCH_ARGS:-"--steps 12 --latency-repeats 0 --beam5-latency-repeats 0 --beam5 0 --stream-sessions 0 --no-cpu-baseline"}
+ARGS=${BENCH_ARGS:-"--full --steps 12 --latency-repeats 0 --beam5-latency-repeats 0 --beam5 0 --stream-sessions 0 --no-cpu-baseline"}
 if [ -n "$PRE_TESTS" ]; then
   if [ "$PRE_TESTS" = all ]; then K=(); else K=(-k "$PRE_TESTS"); fi
   timeout -k 10 400 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread "${K[@]}" > $O/gpu_tests.log 2>&1

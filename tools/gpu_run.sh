@@ -5,7 +5,7 @@
 #   tests       the whole -m gpu suite                      -> $O/gpu_tests.log
 #   smoke       __graft_entry__.smoke()                     -> $O/smoke.log
 #   t:FILES     selected gpu test files/ids (commas -> spaces) -> $O/t_N.log
-#   bench       the default bench line                      -> $O/bench.json
+#   bench       the bench line with every leg (--full)      -> $O/bench.json
 #   prof        one-lane kernel trace of a 3-step bench     -> $O/kernel_summary.txt (+ stats csv)
 #   pmc         FETCH_SIZE / WRITE_SIZE passes (tools/pmc_run.sh) -> $O/pmc/pmc.json
 #   stream      config-5 simulation with host breakdown     -> $O/stream.json
@@ -25,7 +25,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 TAG=$1; shift
 O=gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
-QUICK="--latency-repeats 0 --beam5-latency-repeats 0 --beam5 0 --beam5-steps 0 --realistic-steps 0 --stream-sessions 0 --rest-callers 0 --no-cpu-baseline"
+QUICK="--full --latency-repeats 0 --beam5-latency-repeats 0 --beam5 0 --beam5-steps 0 --realistic-steps 0 --stream-sessions 0 --rest-callers 0 --no-cpu-baseline"
 i=0
 for s in "$@"; do
   i=$((i+1))
@@ -42,7 +42,7 @@ for s in "$@"; do
       timeout -k 10 900 python -u -m pytest $A -m gpu -v --timeout ${T_TIMEOUT:-300} --timeout-method thread -rf --durations=5 > $O/t_$i.log 2>&1
       rc=$?; tail -25 $O/t_$i.log ;;
     bench)
-      timeout -k 10 700 python -u bench.py > $O/bench.json 2> $O/bench.err; rc=$?
+      timeout -k 10 700 python -u bench.py --full > $O/bench.json 2> $O/bench.err; rc=$?
       [ $rc -eq 0 ] && python3 -c "import json;d=json.load(open('$O/bench.json'));print(d['value'],d['ms_per_step'],d.get('p50_latency_ms_b1'),d.get('beam5',{}).get('value'),d.get('streaming',{}).get('transcriptions_per_s'),d['roofline']['frac'])" ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --steps 3 --lanes 1 $QUICK > $O/prof.json 2> $O/prof.err
@@ -64,11 +64,11 @@ for s in "$@"; do
       [ $rc -eq 0 ] && python3 tools/trace_classes.py $O/sprof_$i/run_kernel_trace.csv $O/stream_classes_$i.txt && head -16 $O/stream_classes_$i.txt
       rm -f $O/sprof_$i/run_kernel_trace.csv ;;
     b1)
-      timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/b1prof -o run -- python3 bench.py --steps 1 --warmup 0 --lanes 1 --latency-repeats 4 --latency-warmup 1 --beam5-latency-repeats 0 --beam5 0 --beam5-steps 0 --realistic-steps 0 --stream-sessions 0 --rest-callers 0 --no-cpu-baseline > $O/b1.json 2> $O/b1.err
+      timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/b1prof -o run -- python3 bench.py --full --steps 1 --warmup 0 --lanes 1 --latency-repeats 4 --latency-warmup 1 --beam5-latency-repeats 0 --beam5 0 --beam5-steps 0 --realistic-steps 0 --stream-sessions 0 --rest-callers 0 --no-cpu-baseline > $O/b1.json 2> $O/b1.err
       rc=$?; [ $rc -eq 0 ] && python3 tools/b1_breakdown.py $O/b1prof/run_kernel_trace.csv $((5*445)) > $O/b1_breakdown.txt && head -30 $O/b1_breakdown.txt
       rm -f $O/b1prof/run_kernel_trace.csv ;;
     b1beam)
-      timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/b1bprof -o run -- python3 bench.py --steps 1 --warmup 0 --lanes 1 --latency-repeats 0 --beam5-latency-repeats 4 --latency-warmup 1 --beam5 0 --beam5-steps 0 --realistic-steps 0 --stream-sessions 0 --rest-callers 0 --no-cpu-baseline > $O/b1beam.json 2> $O/b1beam.err
+      timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/b1bprof -o run -- python3 bench.py --full --steps 1 --warmup 0 --lanes 1 --latency-repeats 0 --beam5-latency-repeats 4 --latency-warmup 1 --beam5 0 --beam5-steps 0 --realistic-steps 0 --stream-sessions 0 --rest-callers 0 --no-cpu-baseline > $O/b1beam.json 2> $O/b1beam.err
       rc=$?; [ $rc -eq 0 ] && python3 tools/b1_breakdown.py $O/b1bprof/run_kernel_trace.csv $((5*445)) > $O/b1beam_breakdown.txt && head -40 $O/b1beam_breakdown.txt
       [ $rc -eq 0 ] && python3 tools/step_timeline.py $O/b1bprof/run_kernel_trace.csv beam_update 1500 > $O/b1beam_step_timeline.txt && cat $O/b1beam_step_timeline.txt
       rm -f $O/b1bprof/run_kernel_trace.csv ;;
@@ -84,7 +84,7 @@ for s in "$@"; do
       # the same SQ counter passes over one 64-window greedy step (one lane)
       for f in 1 2; do
         CN=$(sed -e 's/^pmc: *//' tools/pmc_sq$f.txt)
-        timeout -s KILL 300 rocprofv3 --pmc $CN --output-format csv -d $O/pe$f -o run -- python3 bench.py --steps 1 --warmup 0 --lanes 1 --latency-repeats 0 --beam5-latency-repeats 0 --beam5 0 --beam5-steps 0 --realistic-steps 0 --stream-sessions 0 --rest-callers 0 --no-cpu-baseline > $O/pe$f.log 2>&1; rc=$?
+        timeout -s KILL 300 rocprofv3 --pmc $CN --output-format csv -d $O/pe$f -o run -- python3 bench.py --full --steps 1 --warmup 0 --lanes 1 --latency-repeats 0 --beam5-latency-repeats 0 --beam5 0 --beam5-steps 0 --realistic-steps 0 --stream-sessions 0 --rest-callers 0 --no-cpu-baseline > $O/pe$f.log 2>&1; rc=$?
         CSV=$(find $O/pe$f -name '*counter_collection.csv' | head -1)
         [ -n "$CSV" ] && python3 tools/pmc_generic.py $CSV > $O/pmc_enc_$f.txt
         find $O/pe$f -name '*.csv' -delete
@@ -94,7 +94,7 @@ for s in "$@"; do
     pmcb1beam)
       for f in 1 2; do
         CN=$(sed -e 's/^pmc: *//' tools/pmc_sq$f.txt)
-        timeout -s KILL 240 rocprofv3 --pmc $CN --output-format csv -d $O/pq$f -o run -- python3 bench.py --steps 1 --warmup 0 --lanes 1 --batch 4 --latency-repeats 0 --beam5-latency-repeats 1 --latency-warmup 0 --beam5 0 --beam5-steps 0 --realistic-steps 0 --stream-sessions 0 --rest-callers 0 --no-cpu-baseline > $O/pq$f.log 2>&1; rc=$?
+        timeout -s KILL 240 rocprofv3 --pmc $CN --output-format csv -d $O/pq$f -o run -- python3 bench.py --full --steps 1 --warmup 0 --lanes 1 --batch 4 --latency-repeats 0 --beam5-latency-repeats 1 --latency-warmup 0 --beam5 0 --beam5-steps 0 --realistic-steps 0 --stream-sessions 0 --rest-callers 0 --no-cpu-baseline > $O/pq$f.log 2>&1; rc=$?
         CSV=$(find $O/pq$f -name '*counter_collection.csv' | head -1)
         [ -n "$CSV" ] && python3 tools/pmc_generic.py $CSV > $O/pmc_b1beam_$f.txt
         find $O/pq$f -name '*.csv' -delete
