@@ -28,6 +28,15 @@
  *       replaces  resample_pcm16 (src/streaming.py:55-91; scipy resample_poly,
  *                 padtype "line"), called at src/streaming.py:293-294; bit-identical
  *
+ *   osw_set_alignment_heads / osw_align_windows
+ *       replace   WhisperModel.transcribe(..., word_timestamps=True)'s alignment step:
+ *                 faster-whisper's find_alignment -> ctranslate2 Whisper.align(encoder_output,
+ *                 sot_sequence, text_tokens, num_frames, median_filter_width=7) [upstream],
+ *                 i.e. openai-whisper timing.find_alignment; the reference itself calls
+ *                 transcribe without it (src/backends/faster_whisper.py:235-246)
+ *   osw_get_alignment_matrix / osw_debug_dtw
+ *       stage-level read-back and the DTW kernel alone, used only by the parity tests
+ *
  * Conventions: every call returns 0 (OSW_OK) or a negative code; the message of
  * the last failure on the calling thread is osw_last_error().  Host buffers are
  * caller-owned and only read/written during the call (the library copies them).
@@ -260,6 +269,48 @@ int osw_session_step(osw_ctx* ctx, int32_t max_chunks, int32_t refill_min, osw_w
  * already admitted were staged and are unaffected). */
 int osw_session_release_clip(osw_ctx* ctx, int64_t clip);
 int osw_session_end(osw_ctx* ctx);
+
+/* ---- word timestamps: cross-attention alignment + dynamic time warping ----
+ * The alignment heads as n (layer, head) pairs (an HF generation_config.json's
+ * "alignment_heads"); n = 0 restores the default, every head of the last n_text_layer / 2
+ * layers (openai-whisper's default).  Replaces the alignment_heads CTranslate2 reads from
+ * the model's config.json [upstream]. */
+int osw_set_alignment_heads(osw_ctx* ctx, const int32_t* layer_head_pairs, int32_t n);
+
+/* One window to align: the forced sequence is [sot, language, task, no_timestamps,
+ * tokens[0 .. n_tokens), eot] (no previous-text prefix; every text token < eot). */
+typedef struct osw_align_window {
+    int32_t window;               /* index into the last encode / decode / transcribe_batch call */
+    int32_t sot, language, task, no_timestamps, eot;
+    const int32_t* tokens;        /* text tokens, timestamp tokens removed */
+    int32_t n_tokens;             /* 0: no work, empty results */
+    int32_t num_frames;           /* the window's segment_size; F = num_frames / 2 key frames are aligned */
+    int32_t median_filter_width;  /* <= 0: 7 (odd, <= 15) */
+} osw_align_window;
+typedef struct osw_align_result {
+    int32_t* token_frame;         /* [n][stride]: n_tokens + 1 entries per window (the last is eot's); time = frame * 0.02 s */
+    double* token_prob;           /* [n][stride]: n_tokens entries, softmax(logits[:eot])[token]; double, since a
+                                   * forced token can be less likely than fp32 can hold (the device keeps log p) */
+    int32_t stride;               /* >= the largest n_tokens + 1 */
+} osw_align_result;
+/* Teacher-forced decoder pass over the cross-K/V still resident from the last
+ * osw_encode_windows / osw_decode_windows / osw_transcribe_batch call, for n distinct
+ * windows of it: the alignment heads' softmax over the 1500 keys, cropped to F frames,
+ * normalised per (head, frame) over the positions, median-filtered along the frames, averaged
+ * over the heads, rows [no_timestamps, tokens...] kept (the matrix M), then DTW over -M
+ * (transformers' _dynamic_time_warping tie rule) and the first frame of each token.  A
+ * window's result does not depend on the others of the call.  Replaces ctranslate2
+ * Whisper.align as faster-whisper's find_alignment calls it [upstream].  OSW_EINVAL while a
+ * session is open, for a window index the last call does not hold, or n_tokens + 5 > n_text_ctx. */
+int osw_align_windows(osw_ctx* ctx, int32_t n, const osw_align_window* w, osw_align_result* res);
+/* M [T = n_tokens + 1][F] of `window` as the last osw_align_windows call left it (*T = *F = 0
+ * when that call did not align it or it had no text); out may be NULL to query the shape. */
+int osw_get_alignment_matrix(osw_ctx* ctx, int32_t window, float* out, int64_t out_floats, int32_t* T, int32_t* F);
+/* The DTW kernel alone on a host cost matrix x [T][F] (T <= 511, F <= 4096): the path as
+ * text_idx / time_idx [*len], *len <= T + F - 1 (caller buffers of T + F ints).  Replaces
+ * openai-whisper timing.dtw / transformers' _dynamic_time_warping for the parity tests. */
+int osw_debug_dtw(osw_ctx* ctx, const float* x, int32_t T, int32_t F, int32_t* text_idx, int32_t* time_idx,
+                  int32_t* len);
 
 /* Parity helper: one encoder block on x [T][D] fp32 (host), result to y (host). */
 int osw_encoder_layer_debug(osw_ctx* ctx, int32_t layer, const float* x, float* y, int32_t T);

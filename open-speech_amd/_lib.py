@@ -51,6 +51,16 @@ class osw_session_window(C.Structure):
                 ("clip", C.c_int64)]
 
 
+class osw_align_window(C.Structure):
+    _fields_ = [("window", C.c_int32), ("sot", C.c_int32), ("language", C.c_int32), ("task", C.c_int32),
+                ("no_timestamps", C.c_int32), ("eot", C.c_int32), ("tokens", C.POINTER(C.c_int32)),
+                ("n_tokens", C.c_int32), ("num_frames", C.c_int32), ("median_filter_width", C.c_int32)]
+
+
+class osw_align_result(C.Structure):
+    _fields_ = [("token_frame", C.POINTER(C.c_int32)), ("token_prob", C.POINTER(C.c_double)), ("stride", C.c_int32)]
+
+
 class osw_profile(C.Structure):
     _fields_ = [("mel_ms", C.c_double), ("encoder_ms", C.c_double), ("crosskv_ms", C.c_double),
                 ("decoder_ms", C.c_double), ("total_ms", C.c_double), ("decode_steps", C.c_int64),
@@ -91,6 +101,13 @@ _SIGS = {
                                    P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
     "osw_session_release_clip": (C.c_int, [C.c_void_p, C.c_int64]),
     "osw_session_end": (C.c_int, [C.c_void_p]),
+    # word timestamps (replace ctranslate2 Whisper.align as faster-whisper's find_alignment calls it)
+    "osw_set_alignment_heads": (C.c_int, [C.c_void_p, P(C.c_int32), C.c_int32]),
+    "osw_align_windows": (C.c_int, [C.c_void_p, C.c_int32, P(osw_align_window), P(osw_align_result)]),
+    "osw_get_alignment_matrix": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), C.c_int64, P(C.c_int32),
+                                           P(C.c_int32)]),
+    "osw_debug_dtw": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, C.c_int32, P(C.c_int32), P(C.c_int32),
+                                P(C.c_int32)]),
     "osw_encoder_layer_debug": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_float), C.c_int32]),
     "osw_debug_gemm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                  P(C.c_float), C.c_int32, P(C.c_float)]),

@@ -122,8 +122,11 @@ class HipWhisperBackend:
             engines = []
             try:
                 weights = model_store.load_weights(src)
+                heads = model_store.alignment_heads(src)
                 for gpu in self._gpu_ids():
                     eng = factory(src.dims, gpu, max_batch)
+                    if heads and hasattr(eng, "set_alignment_heads"):
+                        eng.set_alignment_heads(heads)   # before sibling(): the lanes inherit them
                     if weights is not None:
                         eng.load_weights(weights)
                     else:
@@ -257,26 +260,37 @@ class HipWhisperBackend:
 
     def _run_inference(self, audio: bytes, model_id: str, task: str = "transcribe", language: str | None = None,
                        response_format: str = "json", temperature: float = 0.0,
-                       prompt: str | None = None) -> dict[str, Any]:
+                       prompt: str | None = None, word_timestamps: bool | None = None,
+                       timestamp_granularities: list | None = None) -> dict[str, Any]:
         m = self._ensure_model(model_id)
+        # faster-whisper's word_timestamps=True / OpenAI's timestamp_granularities[]=word; callers
+        # that pass neither (the unchanged router) get the STT_HIP_WORD_TIMESTAMPS default
+        if word_timestamps is None and timestamp_granularities is None:
+            words = os.environ.get("STT_HIP_WORD_TIMESTAMPS", "0").lower() in ("1", "true", "yes")
+        else:
+            words = bool(word_timestamps) or "word" in (timestamp_granularities or ())
         pcm = decode_audio_bytes(audio)
         opts = TranscribeOptions(task=task, language=language if (language and task == "transcribe") else None,
                                  initial_prompt=prompt or None, temperature=float(temperature or 0.0),
                                  beam_size=int(os.environ.get("STT_HIP_BEAM_SIZE", "5")),
                                  best_of=int(os.environ.get("STT_HIP_BEST_OF", "5")),
-                                 tokens_per_second=self._length_control)
+                                 tokens_per_second=self._length_control, word_timestamps=words)
         res = m.runner.transcribe(pcm, opts)
         return shape_response(task, res, response_format)
 
     def transcribe(self, audio: bytes, model: str, language: str | None = None, response_format: str = "json",
-                   temperature: float = 0.0, prompt: str | None = None) -> dict[str, Any]:
+                   temperature: float = 0.0, prompt: str | None = None, word_timestamps: bool | None = None,
+                   timestamp_granularities: list | None = None) -> dict[str, Any]:
         return self._run_inference(audio, model, task="transcribe", language=language,
-                                   response_format=response_format, temperature=temperature, prompt=prompt)
+                                   response_format=response_format, temperature=temperature, prompt=prompt,
+                                   word_timestamps=word_timestamps, timestamp_granularities=timestamp_granularities)
 
     def translate(self, audio: bytes, model: str, response_format: str = "json", temperature: float = 0.0,
-                  prompt: str | None = None) -> dict[str, Any]:
+                  prompt: str | None = None, word_timestamps: bool | None = None,
+                  timestamp_granularities: list | None = None) -> dict[str, Any]:
         return self._run_inference(audio, model, task="translate", response_format=response_format,
-                                   temperature=temperature, prompt=prompt)
+                                   temperature=temperature, prompt=prompt, word_timestamps=word_timestamps,
+                                   timestamp_granularities=timestamp_granularities)
 
 
 def _default_engine_factory(dims, gpu: int, max_batch: int):

@@ -26,6 +26,7 @@
 
 #include "../../include/osw.h"
 #include "common.h"
+#include "align.h"
 #include "decode.h"
 #include "resln.h"
 
@@ -205,6 +206,25 @@ struct EncBaton {
         if (ev) (void)hipEventDestroy(ev);
     }
 };
+
+// Word-timestamp alignment state of a context (osw_align_windows): the device buffers,
+// sized lazily for the largest call so far, and what the last call aligned
+struct AlignBufs {
+    int *slot = nullptr, *len = nullptr, *forced = nullptr, *lh = nullptr;  // per decoder row; {head, idx} pairs
+    int *slot_len = nullptr, *slot_frames = nullptr, *slot_width = nullptr, *slot_T = nullptr, *path_len = nullptr;
+    int *tf = nullptr, *path = nullptr;
+    float *tokprob = nullptr /* log-probabilities */, *scores = nullptr, *stats = nullptr, *colstats = nullptr, *M = nullptr;
+    unsigned char* trace = nullptr;
+    float *kc32 = nullptr, *vc32 = nullptr;  // fp32 self-K/V cache of the forced pass, [L][cap_rows][H][ctx][64]
+    int cap_slots = 0, cap_pstride = 0, cap_heads = 0, cap_rows = 0;
+    int64_t gen = 0;                // bumps when a buffer moves or the heads change (decode-graph key)
+    std::vector<int> heads;         // the caller's (layer, head) pairs; empty: the default set
+    std::vector<int> layer_first;   // [L + 1] offsets into lh (pairs), heads grouped by layer
+    int n_heads = 0;
+    bool heads_dirty = true;
+    std::vector<int> win, T, F;     // last call: window index, rows and frames of each slot
+    int pstride = 0;
+};
 }  // namespace
 
 struct osw_ctx {
@@ -296,6 +316,9 @@ struct osw_ctx {
     bool capturing = false;
     bool prof_eager = false;  // profiling mode 2: decode steps launched eagerly so the per-kernel timers see them
     bool use_graph = true;
+
+    AlignBufs al;
+    const AlignCapture* acap = nullptr;  // set while osw_align_windows steps the decoder
 
     // profiling
     bool prof = false;
@@ -815,6 +838,17 @@ void encode(osw_ctx* c, const osw_window* wins, int n, const int* slots = nullpt
     c->n_encoded = n;
 }
 
+// Alignment pass only (c->acap set by align()): the raw scaled scores of layer l's alignment
+// heads, from the same q slabs the cross-attention launch beside it reduces
+void align_capture(osw_ctx* c, int l, const float* part, int ks, int nb, int64_t xkv_which) {
+    const AlignCapture& a = *c->acap;
+    const int first = a.layer_first[l], cnt = a.layer_first[l + 1] - first;
+    if (cnt <= 0) return;
+    launch_align_scores(part, ks, WF(c, "dec.l" + std::to_string(l) + ".xq.b"), c->XKV + (2 * l) * xkv_which, nb,
+                        c->d.n_text_head, T_ENC, a.layer_heads + 2 * first, cnt, a.n_heads, c->pos, a.slot, a.len,
+                        a.scores, a.pstride, c->stream);
+}
+
 // ---------------------------- decoder --------------------------------------
 // One decoder row (batch-1 latency; PRO_ROWS): the
 // residual+LayerNorm and GELU-reduce kernels are not launched; each runs as the prologue
@@ -867,7 +901,7 @@ void decoder_step_fused(osw_ctx* c, int nb, int group, bool gather, const SelFus
         const char* e = getenv("OSW_B1_ATTN_TAIL");
         return e && e[0] == '1';
     }();
-    const bool attn_tail = attn_tail_on && nb == 1 && !gather;
+    const bool attn_tail = attn_tail_on && nb == 1 && !gather && !c->acap;
     for (int l = 0; l < L; ++l) {
         const std::string p = "dec.l" + std::to_string(l), pp = "dec.l" + std::to_string(l - 1);
         ProArgs pq = l == 0 ? resln(nullptr, p + ".ln1", true) : resln(WF(c, pp + ".fc2.b"), p + ".ln1", false);
@@ -880,6 +914,11 @@ void decoder_step_fused(osw_ctx* c, int nb, int group, bool gather, const SelFus
             last ^= 1;
         } else {
             fused(PRO_RESLN, pq, p + ".qkv.w", 3 * D, D);
+            if (c->acap)  // alignment pass: fp32 q / k / v and its own fp32 cache (align.hip)
+                launch_align_self_attn(ps[last], ks, WF(c, p + ".qkv.b"), c->acap->kc32 + l * kv_layer,
+                                       c->acap->vc32 + l * kv_layer, c->pos, nb, H, ctx, c->dattn, lo_d, c->sel,
+                                       c->stream);
+            else
             launch_dec_self_attn(ps[last], ks, WF(c, p + ".qkv.b"), c->kc + l * kv_layer, c->vc + l * kv_layer, c->pos,
                                  nb, H, ctx, c->dattn, lo_d, gather ? c->anc : nullptr, group, c->sel, c->stream,
                                  c->row_pos);
@@ -892,6 +931,7 @@ void decoder_step_fused(osw_ctx* c, int nb, int group, bool gather, const SelFus
                                   c->XKV + (2 * l + 1) * xkv_which, nb, H, T_ENC, group, c->dattn, lo_d, c->xws,
                                   c->xticket, c->sel, c->stream);
         }
+        if (c->acap) align_capture(c, l, ps[last], ks, nb, xkv_which);
         plain(c->dattn, p + ".xo.w", D, D);
         fused(PRO_RESLN, resln(WF(c, p + ".xo.b"), p + ".ln3", false), p + ".fc1.w", 4 * D, D);
         ProArgs pg{};
@@ -972,6 +1012,11 @@ bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf 
     for (int l = 0; l < L; ++l) {
         const std::string p = "dec.l" + std::to_string(l);
         int ks = partial(c->xdn, D, p + ".qkv.w", 3 * D, D);
+        if (c->acap)  // alignment pass: fp32 q / k / v and its own fp32 cache (align.hip)
+            launch_align_self_attn(c->part, ks, WF(c, p + ".qkv.b"), c->acap->kc32 + l * kv_layer,
+                                   c->acap->vc32 + l * kv_layer, c->pos, nb, H, ctx, c->dattn, lo_d, c->sel,
+                                   c->stream);
+        else
         launch_dec_self_attn(c->part, ks, WF(c, p + ".qkv.b"), c->kc + l * kv_layer, c->vc + l * kv_layer, c->pos, nb,
                              H, ctx, c->dattn, lo_d, gather ? c->anc : nullptr, group, c->sel, c->stream, c->row_pos);
         ks = partial(c->dattn, D, p + ".o.w", D, D);
@@ -984,6 +1029,7 @@ bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf 
                                   c->XKV + (2 * l + 1) * xkv_which, nb, H, T_ENC, group, c->dattn, lo_d, c->xws,
                                   c->xticket, c->sel, c->stream);
         }
+        if (c->acap) align_capture(c, l, c->part, ks, nb, xkv_which);
         ks = partial(c->dattn, D, p + ".xo.w", D, D);
         launch_dec_resid_ln(c->part, ks, nb, D, WF(c, p + ".xo.b"), c->xd, WF(c, p + ".ln3.g"), WF(c, p + ".ln3.b"),
                             c->xdn, lo_d, nullptr, nullptr, nullptr, nullptr, ctx, d.n_vocab, c->stream);
@@ -1258,6 +1304,211 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r) 
         r->sum_logprob[b] = beam > 1 ? bw[b].best_raw : sp.sum_lp;
         r->no_speech_prob[b] = sp.nsp;
         r->language[b] = sp.lang;
+    }
+}
+
+// ------------------------------ word-timestamp alignment ------------------------------
+// The alignment heads grouped by layer on the device; the default set is every head of the
+// last n_text_layer / 2 layers (openai-whisper's default when a model names none).
+void align_sync_heads(osw_ctx* c) {
+    AlignBufs& A = c->al;
+    const int L = c->d.n_text_layer, H = c->d.n_text_head;
+    if (!A.heads_dirty) return;
+    std::vector<int> hd = A.heads;
+    if (hd.empty())
+        for (int l = L - L / 2; l < L; ++l)
+            for (int h = 0; h < H; ++h) {
+                hd.push_back(l);
+                hd.push_back(h);
+            }
+    const int n = (int)hd.size() / 2;
+    if (!A.lh) A.lh = dalloc<int>((size_t)2 * L * H, c->owned);
+    std::vector<int> lh;
+    A.layer_first.assign(L + 1, 0);
+    for (int l = 0; l < L; ++l) {
+        A.layer_first[l] = (int)lh.size() / 2;
+        for (int i = 0; i < n; ++i)
+            if (hd[2 * i] == l) {
+                lh.push_back(hd[2 * i + 1]);
+                lh.push_back(i);
+            }
+    }
+    A.layer_first[L] = (int)lh.size() / 2;
+    HIPCHK(hipMemcpyAsync(A.lh, lh.data(), lh.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    A.n_heads = n;
+    A.heads_dirty = false;
+    ++A.gen;
+}
+
+void align_reserve(osw_ctx* c, int n_slots, int pstride, int rows) {
+    AlignBufs& A = c->al;
+    const int ctx = c->d.n_text_ctx;
+    auto& o = c->owned;
+    if (rows > A.cap_rows) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        dfree(A.kc32, o);
+        dfree(A.vc32, o);
+        const size_t n = (size_t)c->d.n_text_layer * rows * ctx * c->d.n_text_state;
+        A.kc32 = dalloc<float>(n, o);
+        A.vc32 = dalloc<float>(n, o);
+        A.cap_rows = rows;
+        ++A.gen;
+    }
+    if (!A.slot) {
+        A.slot = dalloc<int>(c->R, o);
+        A.len = dalloc<int>(c->R, o);
+        A.forced = dalloc<int>((size_t)c->R * ctx, o);
+        A.slot_len = dalloc<int>(c->B, o);
+        A.slot_frames = dalloc<int>(c->B, o);
+        A.slot_width = dalloc<int>(c->B, o);
+        A.slot_T = dalloc<int>(c->B, o);
+        A.path_len = dalloc<int>(c->B, o);
+        A.tf = dalloc<int>((size_t)c->B * ctx, o);
+        A.tokprob = dalloc<float>((size_t)c->B * ctx, o);
+    }
+    if (n_slots <= A.cap_slots && pstride <= A.cap_pstride && A.n_heads <= A.cap_heads) return;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    dfree(A.scores, o);
+    dfree(A.stats, o);
+    dfree(A.colstats, o);
+    dfree(A.M, o);
+    dfree(A.trace, o);
+    dfree(A.path, o);
+    const int64_t S = A.cap_slots = std::max(A.cap_slots, n_slots), P = A.cap_pstride = std::max(A.cap_pstride, pstride),
+                  NH = A.cap_heads = std::max(A.cap_heads, A.n_heads);
+    A.scores = dalloc<float>((size_t)(S * NH * P * T_ENC), o);
+    A.stats = dalloc<float>((size_t)(S * NH * P * 2), o);
+    A.colstats = dalloc<float>((size_t)(S * NH * T_ENC * 2), o);
+    A.M = dalloc<float>((size_t)(S * P * T_ENC), o);
+    A.trace = dalloc<unsigned char>((size_t)(S * P * (T_ENC + 1)), o);
+    A.path = dalloc<int>((size_t)(S * 2 * (P + T_ENC)), o);
+    ++A.gen;
+}
+
+// Teacher-forced pass over the resident cross-K/V of the last encode call, one decoder row
+// per encoded window (rows not aligned are marked finished, which every attention kernel
+// skips), through decoder_step with the capture armed; then M, DTW and the read-back.
+void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
+    REQUIRE(n >= 1 && w && r && r->token_frame && r->token_prob, "null align argument");
+    const osw_dims& d = c->d;
+    const int ctx = d.n_text_ctx, V = d.n_vocab, nb = c->n_encoded;
+    REQUIRE(nb >= 1 && nb <= c->R, "no encoded windows are resident (encode or decode first)");
+    REQUIRE(n <= nb, "more windows than the last encode call holds");
+    AlignBufs& A = c->al;
+    std::vector<int> slot(nb, -1), len(nb, 0), forced((size_t)nb * ctx, 0);
+    std::vector<int> s_len, s_fr, s_w, s_T;
+    A.win.clear();
+    A.T.clear();
+    A.F.clear();
+    int pmax = 0;
+    const int eot = w[0].eot;
+    for (int i = 0; i < n; ++i) {
+        const osw_align_window& a = w[i];
+        REQUIRE(a.window >= 0 && a.window < nb, "align: stale window index");
+        REQUIRE(slot[a.window] < 0 && len[a.window] == 0, "align: a window appears twice");
+        REQUIRE(a.n_tokens >= 0 && (a.n_tokens == 0 || a.tokens), "align: bad token list");
+        REQUIRE(a.n_tokens + 5 <= ctx, "align: forced sequence longer than n_text_ctx");
+        REQUIRE(a.n_tokens + 1 <= r->stride, "align: result stride too small");
+        REQUIRE(a.eot == eot && eot > 0 && eot < V, "align: one <|endoftext|> id per call");
+        const int W = a.median_filter_width > 0 ? a.median_filter_width : 7;
+        REQUIRE(W % 2 == 1 && W <= ALIGN_MAX_WIDTH, "align: median filter width must be odd and <= 15");
+        len[a.window] = -1;  // seen
+        if (a.n_tokens == 0) continue;  // no text: no work, empty results
+        const int F = std::min(T_ENC, a.num_frames / 2);
+        REQUIRE(F >= 1, "align: num_frames < 2");
+        for (int t : {a.sot, a.language, a.task, a.no_timestamps}) REQUIRE(t >= 0 && t < V, "align: bad special token");
+        int* f = &forced[(size_t)a.window * ctx];
+        f[0] = a.sot; f[1] = a.language; f[2] = a.task; f[3] = a.no_timestamps;
+        for (int k = 0; k < a.n_tokens; ++k) {
+            REQUIRE(a.tokens[k] >= 0 && a.tokens[k] < eot, "align: text tokens must be below <|endoftext|>");
+            f[4 + k] = a.tokens[k];
+        }
+        f[4 + a.n_tokens] = eot;
+        const int P = a.n_tokens + 5;
+        slot[a.window] = (int)A.win.size();
+        len[a.window] = P;
+        A.win.push_back(a.window);
+        A.T.push_back(a.n_tokens + 1);
+        A.F.push_back(F);
+        s_len.push_back(P);
+        s_fr.push_back(F);
+        s_w.push_back(W);
+        s_T.push_back(a.n_tokens + 1);
+        pmax = std::max(pmax, P);
+    }
+    for (int b = 0; b < nb; ++b) len[b] = std::max(len[b], 0);
+    const int ns = (int)A.win.size();
+    if (ns == 0) return;
+    align_sync_heads(c);
+    const int pstride = (pmax + 15) / 16 * 16;
+    align_reserve(c, ns, pstride, nb);
+    A.pstride = pstride;
+    std::vector<SelState> st(nb);
+    std::vector<int> first(nb);
+    for (int b = 0; b < nb; ++b) {
+        st[b] = SelState{};
+        st[b].done = slot[b] < 0 ? 1 : 0;
+        first[b] = forced[(size_t)b * ctx];
+    }
+    auto up = [&](void* dst, const void* src, size_t bytes) {
+        HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+    };
+    up(A.slot, slot.data(), nb * 4);
+    up(A.len, len.data(), nb * 4);
+    up(A.forced, forced.data(), forced.size() * 4);
+    up(A.slot_len, s_len.data(), ns * 4);
+    up(A.slot_frames, s_fr.data(), ns * 4);
+    up(A.slot_width, s_w.data(), ns * 4);
+    up(A.slot_T, s_T.data(), ns * 4);
+    up(c->sel, st.data(), nb * sizeof(SelState));
+    up(c->cur_tok, first.data(), nb * 4);
+    HIPCHK(hipMemsetAsync(c->pos, 0, 4, c->stream));
+    AlignCapture cap;
+    cap.scores = A.scores; cap.slot = A.slot; cap.len = A.len; cap.layer_heads = A.lh;
+    cap.layer_first = A.layer_first.data(); cap.n_heads = A.n_heads; cap.pstride = pstride;
+    cap.kc32 = A.kc32; cap.vc32 = A.vc32;
+    struct Armed {
+        osw_ctx* c;
+        ~Armed() { c->acap = nullptr; }
+    } armed{c};
+    c->acap = &cap;
+    auto one_step = [&] {
+        decoder_step(c, nb, 1, false, nullptr);
+        launch_align_tail(c->logits, nb, V, eot, ctx, c->pos, A.slot, A.len, A.forced, A.tokprob, c->cur_tok, c->sel,
+                          c->stream);
+        launch_align_bump(c->pos, c->stream);
+    };
+    const int CH = 8;
+    hipGraphExec_t ge = nullptr;
+    if (c->use_graph && !c->prof_eager && pmax >= CH)
+        ge = decode_graph(c, {-77, nb, A.gen, pstride, eot}, one_step, CH);  // its own key: no decode key starts below 1
+    for (int steps = 0; steps < pmax;) {
+        if (ge && pmax - steps >= CH) {
+            HIPCHK(hipGraphLaunch(ge, c->stream));
+            steps += CH;
+        } else {
+            one_step();
+            steps += 1;
+        }
+        HIPCHK(hipGetLastError());
+    }
+    c->acap = nullptr;
+    launch_align_post(A.scores, ns, A.n_heads, pstride, A.slot_len, A.slot_frames, A.slot_width, A.stats, A.colstats,
+                      A.M, c->stream);
+    launch_align_dtw(A.M, (int64_t)pstride * T_ENC, T_ENC, 1, ns, A.slot_T, A.slot_frames, A.trace,
+                     (int64_t)pstride * (T_ENC + 1), A.path, pstride + T_ENC, A.path_len, A.tf, ctx, c->stream);
+    HIPCHK(hipGetLastError());
+    std::vector<int> tf((size_t)ns * ctx);
+    std::vector<float> tp((size_t)ns * ctx);
+    HIPCHK(hipMemcpyAsync(tf.data(), A.tf, tf.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(tp.data(), A.tokprob, tp.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n; ++i) {
+        const int sl = slot[w[i].window];
+        if (sl < 0) continue;
+        for (int k = 0; k <= w[i].n_tokens; ++k) r->token_frame[(size_t)i * r->stride + k] = tf[(size_t)sl * ctx + k];
+        for (int k = 0; k < w[i].n_tokens; ++k) r->token_prob[(size_t)i * r->stride + k] = std::exp((double)tp[(size_t)sl * ctx + k]);
     }
 }
 
@@ -2304,6 +2555,87 @@ int osw_decode_windows(osw_ctx* c, int32_t n, const osw_decode_opts* opts, osw_w
         LaneCall call_(c);
         decode(c, n, opts, res);
         resolve_events(c);
+    });
+}
+
+int osw_set_alignment_heads(osw_ctx* c, const int32_t* layer_head_pairs, int32_t n) {
+    return guard([&] {
+        REQUIRE(c && n >= 0 && (n == 0 || layer_head_pairs), "null argument");
+        std::lock_guard<std::mutex> lk(c->mu);
+        REQUIRE(n <= c->d.n_text_layer * c->d.n_text_head, "more alignment heads than the decoder has");
+        for (int i = 0; i < n; ++i)
+            REQUIRE(layer_head_pairs[2 * i] >= 0 && layer_head_pairs[2 * i] < c->d.n_text_layer &&
+                        layer_head_pairs[2 * i + 1] >= 0 && layer_head_pairs[2 * i + 1] < c->d.n_text_head,
+                    "alignment head out of range");
+        c->al.heads.assign(layer_head_pairs, layer_head_pairs + 2 * (size_t)n);
+        c->al.heads_dirty = true;
+    });
+}
+
+int osw_align_windows(osw_ctx* c, int32_t n, const osw_align_window* w, osw_align_result* res) {
+    return guard([&] {
+        REQUIRE(c, "null ctx");
+        std::lock_guard<std::mutex> lk(c->mu);
+        REQUIRE(!c->sess, "a decode session is open on this context (osw_session_end first)");
+        DeviceScope dev_scope_((c->device));
+        LaneCall call_(c);
+        align(c, n, w, res);
+    });
+}
+
+int osw_get_alignment_matrix(osw_ctx* c, int32_t window, float* out, int64_t out_floats, int32_t* T, int32_t* F) {
+    return guard([&] {
+        REQUIRE(c && T && F, "null argument");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        const AlignBufs& A = c->al;
+        int sl = -1;
+        for (size_t i = 0; i < A.win.size(); ++i)
+            if (A.win[i] == window) sl = (int)i;
+        *T = *F = 0;
+        if (sl < 0) return;  // not aligned by the last call (or no text tokens): an empty matrix
+        *T = A.T[sl];
+        *F = A.F[sl];
+        if (!out) return;
+        REQUIRE(out_floats >= (int64_t)A.T[sl] * A.F[sl], "output buffer too small");
+        HIPCHK(hipMemcpy2DAsync(out, (size_t)A.F[sl] * 4, A.M + (int64_t)sl * A.pstride * T_ENC, (size_t)T_ENC * 4,
+                                (size_t)A.F[sl] * 4, A.T[sl], hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
+int osw_debug_dtw(osw_ctx* c, const float* x, int32_t T, int32_t F, int32_t* text_idx, int32_t* time_idx,
+                  int32_t* len) {
+    return guard([&] {
+        REQUIRE(c && x && text_idx && time_idx && len, "null argument");
+        REQUIRE(T >= 1 && T <= ALIGN_DTW_ROWS && F >= 1 && F <= 4096, "DTW shape out of range");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        std::vector<void*> tmp;
+        const int pcap = T + F;
+        float* xd = dalloc<float>((size_t)T * F, tmp);
+        unsigned char* tr = dalloc<unsigned char>((size_t)(T + 1) * (F + 1), tmp);
+        int* ib = dalloc<int>((size_t)3 + 2 * pcap + T, tmp);  // T, F, path_len, path, token_frame
+        int hdr[3] = {T, F, 0};
+        hipError_t e = hipMemcpyAsync(xd, x, (size_t)T * F * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ib, hdr, sizeof(hdr), hipMemcpyHostToDevice, c->stream);
+        std::vector<int> back((size_t)3 + 2 * pcap);
+        if (e == hipSuccess) {
+            launch_align_dtw(xd, 0, F, 0, 1, ib, ib + 1, tr, 0, ib + 3, pcap, ib + 2, ib + 3 + 2 * pcap, T, c->stream);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(back.data(), ib, back.size() * 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        dfree(xd, tmp);
+        dfree(tr, tmp);
+        dfree(ib, tmp);
+        HIPCHK(e);
+        const int k = back[2];
+        *len = k;
+        for (int i = 0; i < k; ++i) {
+            text_idx[i] = back[3 + pcap - k + i];
+            time_idx[i] = back[3 + pcap + pcap - k + i];
+        }
     });
 }
 

@@ -48,6 +48,25 @@ class WindowOutput:
     logits: np.ndarray | None = field(default=None, repr=False)
 
 
+@dataclass
+class AlignWindow:
+    """One window of ``WhisperEngine.align``: ``window`` indexes the last encode / decode
+    call, ``tokens`` are its text tokens (ids below <|endoftext|>, timestamps removed),
+    ``num_frames`` its segment_size in mel frames."""
+    window: int
+    tokens: list
+    num_frames: int
+    language: int
+    task: str = "transcribe"
+    median_filter_width: int = 7
+
+
+@dataclass
+class Alignment:
+    token_frame: np.ndarray   # [n + 1] first key frame (0.02 s units) of each text token and of <|endoftext|>
+    token_prob: np.ndarray    # [n] softmax(logits[:eot])[token]
+
+
 def _i32p(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
@@ -74,7 +93,10 @@ class WhisperEngine:
     def sibling(self, max_batch: int | None = None) -> "WhisperEngine":
         """A second engine on the same GPU sharing this one's (loaded) weights, with its
         own stream and workspaces: drive it from another thread to overlap batches."""
-        return WhisperEngine(self.dims, self.device, max_batch or self.max_batch, _parent=self)
+        e = WhisperEngine(self.dims, self.device, max_batch or self.max_batch, _parent=self)
+        if getattr(self, "_align_heads", None):
+            e.set_alignment_heads(self._align_heads)
+        return e
 
     # ------------------------------------------------------------ weights
     def set_weight(self, name: str, arr: np.ndarray) -> None:
@@ -331,6 +353,62 @@ class WhisperEngine:
 
     def session_end(self) -> None:
         _lib.check(self.lib.osw_session_end(self.ctx), "osw_session_end")
+
+    # ------------------------------------------------------------ word timestamps
+    def set_alignment_heads(self, heads: list | None) -> None:
+        """The cross-attention heads word timing reads, as (layer, head) pairs; None or
+        empty: every head of the last ``n_text_layer // 2`` layers (upstream's default)."""
+        pairs = [(int(l), int(h)) for l, h in (heads or [])]
+        arr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1) if pairs else np.zeros(2, np.int32)
+        _lib.check(self.lib.osw_set_alignment_heads(self.ctx, _i32p(arr), len(pairs)), "osw_set_alignment_heads")
+        self._align_heads = pairs
+
+    def align(self, windows: list) -> list:
+        """Cross-attention alignment + DTW (osw_align_windows) of ``AlignWindow``s over the
+        cross-K/V resident from the last encode / decode call; one ``Alignment`` each."""
+        if not windows:
+            return []
+        st = self.st
+        stride = max(len(w.tokens) for w in windows) + 1
+        toks = [np.ascontiguousarray(w.tokens if len(w.tokens) else [0], dtype=np.int32) for w in windows]
+        arr = (_lib.osw_align_window * len(windows))()
+        for i, w in enumerate(windows):
+            arr[i] = _lib.osw_align_window(
+                window=int(w.window), sot=st.sot, language=int(w.language),
+                task=st.transcribe if w.task == "transcribe" else st.translate, no_timestamps=st.no_timestamps,
+                eot=st.eot, tokens=_i32p(toks[i]), n_tokens=len(w.tokens), num_frames=int(w.num_frames),
+                median_filter_width=int(w.median_filter_width))
+        tf = np.zeros((len(windows), stride), np.int32)
+        tp = np.zeros((len(windows), stride), np.float64)
+        res = _lib.osw_align_result(token_frame=_i32p(tf), token_prob=tp.ctypes.data_as(C.POINTER(C.c_double)),
+                                    stride=stride)
+        _lib.check(self.lib.osw_align_windows(self.ctx, len(windows), arr, C.byref(res)), "osw_align_windows")
+        del toks
+        return [Alignment(tf[i, :len(w.tokens) + 1].copy() if len(w.tokens) else np.zeros(0, np.int32),
+                          tp[i, :len(w.tokens)].copy()) for i, w in enumerate(windows)]
+
+    def alignment_matrix(self, window: int) -> np.ndarray:
+        """M [n + 1][F] of ``window`` as the last ``align`` call left it (parity tests)."""
+        T, F = C.c_int32(), C.c_int32()
+        _lib.check(self.lib.osw_get_alignment_matrix(self.ctx, int(window), None, 0, C.byref(T), C.byref(F)),
+                   "osw_get_alignment_matrix")
+        out = np.empty((T.value, F.value), np.float32)
+        if out.size:
+            _lib.check(self.lib.osw_get_alignment_matrix(self.ctx, int(window),
+                                                         out.ctypes.data_as(C.POINTER(C.c_float)), out.size,
+                                                         C.byref(T), C.byref(F)), "osw_get_alignment_matrix")
+        return out
+
+    def debug_dtw(self, x: np.ndarray):
+        """The DTW kernel alone on a cost matrix x [T][F]: (text_indices, time_indices)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        T, F = x.shape
+        ti = np.zeros(T + F, np.int32)
+        fi = np.zeros(T + F, np.int32)
+        n = C.c_int32()
+        _lib.check(self.lib.osw_debug_dtw(self.ctx, x.ctypes.data_as(C.POINTER(C.c_float)), T, F, _i32p(ti),
+                                          _i32p(fi), C.byref(n)), "osw_debug_dtw")
+        return ti[:n.value].copy(), fi[:n.value].copy()
 
     def debug_gemm(self, A: np.ndarray, W: np.ndarray, variant: int = 0, iters: int = 1):
         """C = A·Wᵀ (fp16 in, fp32 out) through one GEMM kernel variant; returns (C, mean ms)."""

@@ -89,6 +89,29 @@ def resolve(model_id: str, model_dir: str | None = None) -> ModelSource:
                             "this backend never downloads")
 
 
+def alignment_heads(src: ModelSource) -> list | None:
+    """The (layer, head) pairs word timing reads: ``alignment_heads`` of an HF checkpoint's
+    ``generation_config.json`` or of a CTranslate2 directory's ``config.json`` (what
+    CTranslate2's ``align`` uses [upstream]).  None: the engine's default, every head of the
+    last ``n_text_layer // 2`` layers (random-weight models have no file to read)."""
+    if not src.path:
+        return None
+    for name in ("generation_config.json", "config.json"):
+        f = os.path.join(src.path, name)
+        if not os.path.exists(f):
+            continue
+        try:
+            with open(f) as fh:
+                heads = json.load(fh).get("alignment_heads")
+        except (OSError, ValueError, AttributeError):
+            continue
+        if heads:
+            pairs = [(int(l), int(h)) for l, h in heads]
+            if all(0 <= l < src.dims.n_text_layer and 0 <= h < src.dims.n_text_head for l, h in pairs):
+                return pairs
+    return None
+
+
 def load_weights(src: ModelSource) -> dict | None:
     """Canonical weights for a resolved source (None for random init)."""
     if src.kind == "hf":

@@ -18,9 +18,17 @@ the best kept, and the previous-text prompt reset when temperature > 0.5):
   skip window if no_speech_prob > 0.6 and avg_logprob < -1.0  (seek += segment_size)
   split at consecutive timestamp pairs; single timestamp ending -> seek += segment_size,
   else seek += last_timestamp_position * 2; drop segments with start == end or blank text
+
+Word timestamps (``TranscribeOptions.word_timestamps``; faster-whisper ``add_word_timestamps``
+/ ``find_alignment`` / ``merge_punctuations``, restated from the upstream code, not pinned):
+after a window's decode its text tokens are aligned on the GPU (``engine.align``), split
+into words, clamped and attached to the window's segments, and the seek rule gains
+  not single_timestamp_ending and last_word_end > time_offset -> seek = round(last_word_end * 100)
+with ``last_speech_timestamp`` carried from window to window.
 """
 from __future__ import annotations
 
+import itertools
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -58,12 +66,24 @@ class TranscribeOptions:
     # bench-only length control (HipWhisperBackend(length_control=...)): random weights never emit
     # <|endoftext|>, so each window's decode is cut at ceil(rate * window seconds) + 2
     tokens_per_second: float | None = None
+    # per-word start / end / probability on every segment (faster-whisper word_timestamps=True)
+    word_timestamps: bool = False
+    prepend_punctuations: str = "\"'“¿([{-"
+    append_punctuations: str = "\"'.。,，!！?？:：”)]}、"
 
     def key(self):
         return (self.task, self.language, self.initial_prompt, self.condition_on_previous_text,
                 self.without_timestamps, tuple(self.suppress_tokens), self.suppress_blank, self.beam_size,
                 self.patience, self.length_penalty, self.temperature, self.best_of, self.tokens_per_second,
-                self.max_new_tokens)
+                self.max_new_tokens, self.word_timestamps, self.prepend_punctuations, self.append_punctuations)
+
+
+@dataclass
+class Word:
+    start: float
+    end: float
+    word: str
+    probability: float
 
 
 @dataclass
@@ -78,6 +98,7 @@ class Segment:
     avg_logprob: float
     compression_ratio: float
     no_speech_prob: float
+    words: list | None = None      # [Word] with word_timestamps, else None
 
 
 @dataclass
@@ -130,6 +151,7 @@ class _ClipState:
     lang_token: int | None = None
     done: bool = False
     result: ClipResult = field(default_factory=ClipResult)
+    last_speech_timestamp: float = 0.0   # word timestamps: end of the last word so far
 
 
 def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: WhisperTokenizer,
@@ -188,8 +210,25 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
                 calls += 1
                 prefixes = [p for _, p in chunk] if _plen else None
                 outs = engine.decode(len(chunk), cfg, prefix=prefixes, languages=langs)
-                for (s, _), w, out in zip(chunk, wins, outs):
-                    _consume(s, w, out, opts, tok)
+                if not opts.word_timestamps:
+                    for (s, _), w, out in zip(chunk, wins, outs):
+                        _consume(s, w, out, opts, tok)
+                    continue
+                # word timestamps: one alignment call for the chunk's windows while their
+                # cross-K/V is still resident, then the segments with their words
+                from .engine import AlignWindow
+                plans = [_plan(s, w, out, opts, tok) for (s, _), w, out in zip(chunk, wins, outs)]
+                req = [(i, p) for i, p in enumerate(plans) if p is not None and p["text_tokens"]]
+                # the forced sequence adds 5 positions: a window that decoded more text tokens than
+                # fit (a model that never emits <|endoftext|>) aligns the ones that do
+                room = 448 - 5
+                als = engine.align([AlignWindow(window=i, tokens=p["text_tokens"][:room], num_frames=wins[i][2],
+                                                language=outs[i].language, task=opts.task)
+                                    for i, p in req]) if req else []
+                aligned = {i: _pad_alignment(a, len(p["text_tokens"])) for (i, p), a in zip(req, als)}
+                for i, ((s, _), w, out) in enumerate(zip(chunk, wins, outs)):
+                    if plans[i] is not None:
+                        _apply(s, w, out, opts, tok, plans[i], aligned.get(i))
     for s in states:
         code = tok.language_code(s.lang_token) if s.lang_token is not None else (opts.language or "en")
         s.result.language = code
@@ -204,6 +243,8 @@ def session_supported(opts: TranscribeOptions) -> bool:
     """Decode sessions (osw_session_*) hold one decode configuration for every window:
     temperature 0, beam_size <= 5, and no max_new_tokens (whose max_length depends on
     each window's prompt length)."""
+    if opts.word_timestamps:   # the alignment pass needs the window's cross-K/V of a batched decode call
+        return False
     return not (opts.temperature > 0) and opts.max_new_tokens is None and 1 <= int(opts.beam_size) <= 5
 
 
@@ -248,6 +289,14 @@ def finish_clip(s: _ClipState, opts: TranscribeOptions, tok: WhisperTokenizer) -
 
 
 def _consume(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperTokenizer) -> None:
+    plan = _plan(s, win, out, opts, tok)
+    if plan is not None:
+        _apply(s, win, out, opts, tok, plan, None)
+
+
+def _plan(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperTokenizer):
+    """The window's segments before they are kept (None: the window was skipped as silence),
+    with the text tokens word timing aligns."""
     st = tok.special
     _, seek, segment_size = win
     if s.lang_token is None:
@@ -263,10 +312,28 @@ def _consume(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperToken
         if skip:
             s.seek = seek + segment_size
             s.done = s.seek >= s.content_frames
-            return
+            return None
     time_offset = seek * FRAME_SEC
-    segs, new_seek, _ = split_segments_by_timestamps(tokens, st.timestamp_begin, time_offset, segment_size,
-                                                     segment_size * FRAME_SEC, seek)
+    segs, new_seek, single_ending = split_segments_by_timestamps(tokens, st.timestamp_begin, time_offset, segment_size,
+                                                                 segment_size * FRAME_SEC, seek)
+    text_tokens = [int(t) for sg in segs for t in sg["tokens"] if t < st.eot]
+    return dict(segs=segs, new_seek=new_seek, single_ending=single_ending, avg_logprob=avg_logprob, cr=cr,
+                text_tokens=text_tokens, time_offset=time_offset)
+
+
+def _apply(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperTokenizer, plan: dict, alignment) -> None:
+    """Keep the planned segments (with their words when ``alignment`` is given) and move the seek."""
+    _, seek, segment_size = win
+    segs, new_seek, avg_logprob, cr = plan["segs"], plan["new_seek"], plan["avg_logprob"], plan["cr"]
+    if opts.word_timestamps:
+        lang = tok.language_code(s.lang_token) if s.lang_token is not None else opts.language
+        s.last_speech_timestamp = add_word_timestamps(segs, tok, alignment, lang, opts.prepend_punctuations,
+                                                      opts.append_punctuations, s.last_speech_timestamp)
+        last_word_end = _last_word_end(segs)
+        if not plan["single_ending"] and last_word_end is not None and last_word_end > plan["time_offset"]:
+            new_seek = round(last_word_end / FRAME_SEC)
+        if last_word_end is not None:
+            s.last_speech_timestamp = last_word_end
     for sg in segs:
         t = sg["tokens"]
         txt = tok.decode(t)
@@ -276,15 +343,154 @@ def _consume(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperToken
         s.result.segments.append(Segment(id=len(s.result.segments), seek=seek, start=sg["start"], end=sg["end"],
                                          text=txt, tokens=list(t), temperature=opts.temperature,
                                          avg_logprob=avg_logprob, compression_ratio=cr,
-                                         no_speech_prob=out.no_speech_prob))
+                                         no_speech_prob=out.no_speech_prob,
+                                         words=[Word(**w) for w in sg["words"]] if "words" in sg else None))
     if not opts.condition_on_previous_text or opts.temperature > opts.prompt_reset_on_temperature:
         s.prompt_reset_since = len(s.all_tokens)
     s.seek = new_seek
     s.done = s.seek >= s.content_frames
 
 
+# ------------------------------------------------------------ word timestamps
+SENTENCE_END_MARKS = ".。!！?？"
+
+
+def find_alignment(tok: WhisperTokenizer, text_tokens: list, alignment, language: str | None) -> list:
+    """faster-whisper ``find_alignment`` after CTranslate2's ``align`` [upstream]: words with
+    the first frame of their first token as start, of the next word's first token as end
+    (the <|endoftext|> frame for the last word), and the mean token probability."""
+    if alignment is None or not text_tokens:
+        return []
+    words, word_tokens = tok.split_to_word_tokens(list(text_tokens) + [tok.special.eot], language)
+    if len(word_tokens) <= 1:
+        return []
+    bounds = np.pad(np.cumsum([len(t) for t in word_tokens[:-1]]), (1, 0))
+    times = np.asarray(alignment.token_frame, dtype=np.float64) * TIME_PRECISION
+    probs = np.asarray(alignment.token_prob, dtype=np.float64)
+    return [dict(word=w, tokens=list(t), start=float(times[i]), end=float(times[j]),
+                 probability=float(np.mean(probs[i:j])))
+            for w, t, i, j in zip(words, word_tokens, bounds[:-1], bounds[1:])]
+
+
+def merge_punctuations(alignment: list, prepended: str, appended: str) -> None:
+    """faster-whisper ``merge_punctuations`` [upstream], in place: merged words keep their
+    own times, the absorbed entry becomes an empty word without tokens."""
+    i, j = len(alignment) - 2, len(alignment) - 1
+    while i >= 0:
+        prev, foll = alignment[i], alignment[j]
+        if prev["word"].startswith(" ") and prev["word"].strip() in prepended:
+            foll["word"] = prev["word"] + foll["word"]
+            foll["tokens"] = prev["tokens"] + foll["tokens"]
+            prev["word"] = ""
+            prev["tokens"] = []
+        else:
+            j = i
+        i -= 1
+    i, j = 0, 1
+    while j < len(alignment):
+        prev, foll = alignment[i], alignment[j]
+        if not prev["word"].endswith(" ") and foll["word"] in appended:
+            prev["word"] = prev["word"] + foll["word"]
+            prev["tokens"] = prev["tokens"] + foll["tokens"]
+            foll["word"] = ""
+            foll["tokens"] = []
+        else:
+            i = j
+        j += 1
+
+
+def add_word_timestamps(segs: list, tok: WhisperTokenizer, alignment, language: str | None, prepend: str,
+                        append: str, last_speech_timestamp: float) -> float:
+    """faster-whisper ``add_word_timestamps`` [upstream] for one window: ``segs`` are the
+    window's segment dicts (``split_segments_by_timestamps``), each gains ``"words"`` and may
+    have its start / end moved to its words; returns the new last_speech_timestamp."""
+    if not segs:
+        return last_speech_timestamp
+    per_seg = [[t for t in sg["tokens"] if t < tok.special.eot] for sg in segs]
+    text_tokens = list(itertools.chain.from_iterable(per_seg))
+    words_all = find_alignment(tok, text_tokens, alignment, language)
+    durations = np.array([w["end"] - w["start"] for w in words_all])
+    durations = durations[durations.nonzero()]
+    median_duration = min(0.7, float(np.median(durations))) if len(durations) else 0.0
+    max_duration = median_duration * 2
+    if len(durations):
+        # words at sentence boundaries no longer than twice the median word duration
+        for i in range(1, len(words_all)):
+            w = words_all[i]
+            if w["end"] - w["start"] > max_duration:
+                if w["word"] in SENTENCE_END_MARKS:
+                    w["end"] = w["start"] + max_duration
+                elif words_all[i - 1]["word"] in SENTENCE_END_MARKS:
+                    w["start"] = w["end"] - max_duration
+    merge_punctuations(words_all, prepend, append)
+    time_offset = segs[0]["seek"] * FRAME_SEC
+    wi = 0
+    for sg, toks in zip(segs, per_seg):
+        saved, words = 0, []
+        while wi < len(words_all) and saved < len(toks):
+            t = words_all[wi]
+            if t["word"]:
+                words.append(dict(word=t["word"], start=round(time_offset + t["start"], 2),
+                                  end=round(time_offset + t["end"], 2), probability=t["probability"]))
+            saved += len(t["tokens"])
+            wi += 1
+        if words:
+            # the first and second word after a pause no longer than twice the median duration
+            if words[0]["end"] - last_speech_timestamp > median_duration * 4 and (
+                    words[0]["end"] - words[0]["start"] > max_duration
+                    or (len(words) > 1 and words[1]["end"] - words[0]["start"] > max_duration * 2)):
+                if len(words) > 1 and words[1]["end"] - words[1]["start"] > max_duration:
+                    boundary = max(words[1]["end"] / 2, words[1]["end"] - max_duration)
+                    words[0]["end"] = words[1]["start"] = boundary
+                words[0]["start"] = max(0, words[0]["end"] - max_duration)
+            # prefer the segment-level start / end when the first / last word is too long
+            if sg["start"] < words[0]["end"] and sg["start"] - 0.5 > words[0]["start"]:
+                words[0]["start"] = max(0, min(words[0]["end"] - median_duration, sg["start"]))
+            else:
+                sg["start"] = words[0]["start"]
+            if sg["end"] > words[-1]["start"] and sg["end"] + 0.5 < words[-1]["end"]:
+                words[-1]["end"] = max(words[-1]["start"] + median_duration, sg["end"])
+            else:
+                sg["end"] = words[-1]["end"]
+            last_speech_timestamp = sg["end"]
+        sg["words"] = words
+    return last_speech_timestamp
+
+
+def _pad_alignment(a, n: int):
+    """Text tokens beyond the aligned ones take the <|endoftext|> frame and probability 0."""
+    k = len(a.token_prob)
+    if k >= n:
+        return a
+    from .engine import Alignment
+    tf = np.asarray(a.token_frame)
+    return Alignment(np.concatenate([tf[:k], np.full(n - k + 1, tf[-1], tf.dtype)]),
+                     np.concatenate([np.asarray(a.token_prob, np.float64), np.zeros(n - k)]))
+
+
+def _last_word_end(segs: list):
+    """faster-whisper ``get_end`` [upstream]: the last word's end, else the last segment's."""
+    for sg in reversed(segs):
+        for w in reversed(sg.get("words") or []):
+            return w["end"]
+    return segs[-1]["end"] if segs else None
+
+
 def verbose_dict(task: str, res: ClipResult) -> dict:
-    """The ``verbose_json`` shape of ``src/backends/faster_whisper.py:251-272``."""
+    """The ``verbose_json`` shape of ``src/backends/faster_whisper.py:251-272``; with word
+    timestamps every segment gains ``words`` and the response a flat ``words`` list (the
+    OpenAI ``timestamp_granularities[]=word`` shape)."""
+    out = _verbose_dict(task, res)
+    if any(sg.words is not None for sg in res.segments):
+        for d, sg in zip(out["segments"], res.segments):
+            d["words"] = [{"start": w.start, "end": w.end, "word": w.word, "probability": w.probability}
+                          for w in (sg.words or [])]
+        out["words"] = [{"word": w.word, "start": w.start, "end": w.end}
+                        for sg in res.segments for w in (sg.words or [])]
+    return out
+
+
+def _verbose_dict(task: str, res: ClipResult) -> dict:
     full = "".join(sg.text for sg in res.segments).strip()
     return {
         "task": task, "language": res.language, "duration": res.duration, "text": full,

@@ -14,6 +14,7 @@ tokenizer in this image to recompute it).
 from __future__ import annotations
 
 import os
+import string
 import zlib
 
 from .dims import LANGUAGE_CODES, SpecialTokens
@@ -29,6 +30,7 @@ NON_SPEECH_TOKENS_MULTILINGUAL = (
 _SYMBOLS = list('"#()*+/:;<=>@[\\]^_`{|}~「」『』')
 _SYMBOLS += "<< >> <<< >>> -- --- -( -[ (' (\" (( )) ((( ))) [[ ]] {{ }} ♪♪ ♪♪♪".split()
 _MISC = set("♩♪♫♬♭♮♯")
+UNSPACED_LANGUAGES = frozenset({"zh", "ja", "th", "lo", "my", "yue"})
 
 
 class WhisperTokenizer:
@@ -57,6 +59,65 @@ class WhisperTokenizer:
         if self._tok is None:
             return "".join(f"<|{t}|>" for t in text_tokens)
         return self._tok.decode(text_tokens, skip_special_tokens=False)
+
+    def _decode_with_specials(self, tokens) -> str:
+        """Text tokens decoded; <|endoftext|> kept as its own marker (it closes the word
+        list of ``split_to_word_tokens``); other ids above it dropped."""
+        out, run = [], []
+        for t in tokens:
+            t = int(t)
+            if t < self.special.eot:
+                run.append(t)
+                continue
+            if run:
+                out.append(self.decode(run))
+                run = []
+            if t == self.special.eot:
+                out.append("<|endoftext|>")
+        if run:
+            out.append(self.decode(run))
+        return "".join(out)
+
+    def split_tokens_on_unicode(self, tokens):
+        """faster-whisper ``Tokenizer.split_tokens_on_unicode`` [upstream]: a word closes
+        where the tokens so far decode to complete UTF-8 (no U+FFFD that the full text
+        does not have at the same place)."""
+        full = self._decode_with_specials(tokens)
+        rep = "\ufffd"
+        words, word_tokens, cur, offset = [], [], [], 0
+        for t in tokens:
+            cur.append(int(t))
+            dec = self._decode_with_specials(cur)
+            at = dec.find(rep)
+            if at < 0 or (at + offset < len(full) and full[at + offset] == rep):
+                words.append(dec)
+                word_tokens.append(cur)
+                cur = []
+                offset += len(dec)
+        return words, word_tokens
+
+    def split_tokens_on_spaces(self, tokens):
+        """faster-whisper ``Tokenizer.split_tokens_on_spaces`` [upstream]: sub-words join the
+        word before them unless they start with a space, are punctuation or are special."""
+        words, word_tokens = [], []
+        for sub, sub_tokens in zip(*self.split_tokens_on_unicode(tokens)):
+            special = sub_tokens[0] >= self.special.eot
+            if special or sub.startswith(" ") or sub.strip() in string.punctuation or not words:
+                words.append(sub)
+                word_tokens.append(list(sub_tokens))
+            else:
+                words[-1] += sub
+                word_tokens[-1].extend(sub_tokens)
+        return words, word_tokens
+
+    def split_to_word_tokens(self, tokens, language: str | None = None):
+        """(words, tokens of each word) of ``tokens`` (text ids, usually closed by
+        <|endoftext|>, which becomes the last pseudo-word): faster-whisper
+        ``Tokenizer.split_to_word_tokens`` [upstream].  Languages written without spaces
+        split at Unicode boundaries, the rest at spaces with punctuation kept apart."""
+        if language in UNSPACED_LANGUAGES:
+            return self.split_tokens_on_unicode(tokens)
+        return self.split_tokens_on_spaces(tokens)
 
     def non_speech_tokens(self) -> tuple:
         if self._tok is None:

@@ -1,0 +1,264 @@
+"""Word timestamps on the GPU: the DTW kernel alone, the alignment matrix M against the
+fp32 transformers goldens (tools/make_align_golden.py), path consistency, token
+probabilities, batch invariance, alignment heads, and decode left undisturbed.
+
+Bounds: DTW paths are exact (integer matrices whose sums are exact in fp32, and fp32
+random matrices where the GPU adds the same two fp32 numbers per cell); ``matrix_tol``
+comes from the golden file (measured on the reference alone, see the tool); token
+probabilities use the project's log-softmax bar.
+"""
+import os
+
+import numpy as np
+import pytest
+
+from open_speech_amd import dims as D
+from open_speech_amd import synth, weights
+from open_speech_amd.engine import AlignWindow, DecodeConfig, WhisperEngine
+from open_speech_amd.tokenizer import WhisperTokenizer, get_suppressed_tokens
+
+import align_ref
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
+LSM_TOL = 1e-3   # tests/test_gpu_turbo.py
+
+
+def load_gold(name):
+    z = np.load(os.path.join(GOLD, name))
+    wins = []
+    for i in range(int(z["n_windows"])):
+        wins.append({k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(f"w{i}/")})
+    return z, wins
+
+
+@pytest.fixture(scope="module")
+def tiny():
+    d = D.TINY_TEST
+    eng = WhisperEngine(d, device=0, max_batch=4)
+    eng.load_weights(weights.random_weights(d, seed=1234, emb_std=0.5))
+    z, wins = load_gold("align_tiny.npz")
+    eng.log_mel([synth.chirp_clip(3, 30.0)])
+    yield d, eng, z, wins
+    eng.close()
+
+
+def encode_tiny(eng, wins):
+    eng.encode([(0, int(w["seek"]), int(w["num_frames"])) for w in wins])
+
+
+def awin(i, w, lang, tokens=None):
+    toks = w["forced"][4:-1].tolist() if tokens is None else tokens
+    return AlignWindow(window=i, tokens=toks, num_frames=int(w["num_frames"]), language=int(lang))
+
+
+@pytest.fixture(scope="module")
+def tiny_aligned(tiny):
+    """The three golden windows aligned in one call: (alignments, matrices), computed once."""
+    d, eng, z, wins = tiny
+    encode_tiny(eng, wins)
+    al = eng.align([awin(i, w, z["language"]) for i, w in enumerate(wins)])
+    return al, [eng.alignment_matrix(i) for i in range(len(wins))]
+
+
+DTW_SHAPES = [(1, 1), (2, 1), (1, 7), (5, 3), (38, 1500), (257, 300), (445, 1500)]
+
+
+@pytest.mark.parametrize("shape", DTW_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("kind", ["ties", "random"])
+def test_dtw_kernel_equals_numpy(tiny, shape, kind):
+    d, eng, _, _ = tiny
+    T, F = shape
+    rng = np.random.default_rng(100 * T + F)
+    x = align_ref.tie_matrix(rng, T, F) if kind == "ties" else rng.standard_normal((T, F)).astype(np.float32)
+    ti, fi = eng.debug_dtw(x)
+    rt, rf = align_ref.dtw(x)
+    assert len(ti) == len(rt)
+    np.testing.assert_array_equal(ti, rt)
+    np.testing.assert_array_equal(fi, rf)
+
+
+def check_window(eng, w, al, M):
+    n = len(w["forced"]) - 5
+    assert M.shape == w["M"].shape == (n + 1, int(w["num_frames"]) // 2)
+    delta = float(np.abs(M - w["M"]).max())
+    tol = float(w["matrix_tol"])
+    print(f"n {n} F {M.shape[1]}: max |M_gpu - M_gold| {delta:.4g} (matrix_tol {tol:.4g})")
+    assert delta <= tol
+    # the GPU's token_frame is the DTW of the GPU's own M
+    ti, fi = align_ref.dtw(-M)
+    np.testing.assert_array_equal(al.token_frame, align_ref.token_frames(ti, fi))
+    gt, gf = eng.debug_dtw(-M)
+    np.testing.assert_array_equal(gt, ti)
+    np.testing.assert_array_equal(gf, fi)
+    # its cost on the golden matrix is within the elementwise bound of the golden path's
+    c_gpu = align_ref.path_cost(-w["M"], ti, fi)
+    c_gold = align_ref.path_cost(-w["M"], w["text_indices"], w["time_indices"])
+    assert c_gpu - c_gold <= 2 * len(ti) * delta
+    same = int((al.token_frame == w["token_frame"]).sum())
+    print(f"token_frame entries equal to the golden's: {same} of {n + 1}; path cost {c_gpu:.4f} vs {c_gold:.4f}")
+    return delta
+
+
+def check_probs(w, al):
+    err = np.abs(np.log(al.token_prob.astype(np.float64)) - np.log(w["token_prob"])).max()
+    print(f"max |d log token_prob| {err:.3e}")
+    assert err <= LSM_TOL
+
+
+@pytest.mark.parametrize("i", [0, 1, 2])
+def test_tiny_matrix_path_and_probs(tiny, tiny_aligned, i):
+    d, eng, z, wins = tiny
+    al, Ms = tiny_aligned
+    check_window(eng, wins[i], al[i], Ms[i])
+
+
+@pytest.mark.parametrize("i", [0, 1, 2])
+def test_tiny_token_probs(tiny, tiny_aligned, i):
+    """|log token_prob_gpu - log token_prob_gold| <= 1e-3, the log-softmax bar stated for the
+    benchmarked model, applied to the tiny-dims windows as well.  The forced pass keeps its
+    self-attention q / k / v in fp32: with the decode path's fp16 q and self-K/V cache the
+    5-frame window measured 1.33e-3 (the fp16-emulating oracle gives 1.34e-3 from that
+    rounding alone)."""
+    d, eng, z, wins = tiny
+    al, Ms = tiny_aligned
+    check_probs(wins[i], al[i])
+
+
+def test_tiny_batch_invariance(tiny, tiny_aligned):
+    d, eng, z, wins = tiny
+    al, Ms = tiny_aligned
+    encode_tiny(eng, wins)
+    for i, w in enumerate(wins):
+        one = eng.align([awin(i, w, z["language"])])[0]
+        np.testing.assert_array_equal(eng.alignment_matrix(i), Ms[i])
+        np.testing.assert_array_equal(one.token_frame, al[i].token_frame)
+        np.testing.assert_array_equal(one.token_prob, al[i].token_prob)
+    # a window without text returns empty results and leaves its neighbours unchanged
+    mixed = eng.align([awin(0, wins[0], z["language"]), awin(1, wins[1], z["language"], tokens=[]),
+                       awin(2, wins[2], z["language"])])
+    assert mixed[1].token_frame.size == 0 and mixed[1].token_prob.size == 0
+    assert eng.alignment_matrix(1).size == 0
+    for i in (0, 2):
+        np.testing.assert_array_equal(eng.alignment_matrix(i), Ms[i])
+        np.testing.assert_array_equal(mixed[i].token_frame, al[i].token_frame)
+        np.testing.assert_array_equal(mixed[i].token_prob, al[i].token_prob)
+
+
+def test_tiny_align_after_beam_equals_after_greedy(tiny, tiny_aligned):
+    d, eng, z, wins = tiny
+    al, Ms = tiny_aligned
+    sup = get_suppressed_tokens(WhisperTokenizer(d.n_vocab), [-1])
+    for beam in (1, 5):
+        eng.encode([(0, 0, 3000)])
+        eng.decode(1, DecodeConfig(suppress_tokens=sup, max_length=24, beam_size=beam))
+        one = eng.align([awin(0, wins[0], z["language"])])[0]
+        np.testing.assert_array_equal(eng.alignment_matrix(0), Ms[0])
+        np.testing.assert_array_equal(one.token_frame, al[0].token_frame)
+        np.testing.assert_array_equal(one.token_prob, al[0].token_prob)
+
+
+def test_tiny_alignment_heads(tiny, tiny_aligned):
+    d, eng, z, wins = tiny
+    al, Ms = tiny_aligned
+    L, H = d.n_text_layer, d.n_text_head
+    encode_tiny(eng, wins)
+    try:
+        eng.set_alignment_heads([(L - 1, 0)])
+        eng.align([awin(i, w, z["language"]) for i, w in enumerate(wins)])
+        for i, w in enumerate(wins):
+            delta = float(np.abs(eng.alignment_matrix(i) - w["M_head"]).max())
+            print(f"single head, window {i}: max |dM| {delta:.4g} (matrix_tol {float(w['matrix_tol']):.4g})")
+            assert delta <= float(w["matrix_tol"])
+        # the default is every head of the last half of the layers
+        eng.set_alignment_heads([(l, h) for l in range(L - L // 2, L) for h in range(H)])
+        eng.align([awin(i, w, z["language"]) for i, w in enumerate(wins)])
+        for i in range(len(wins)):
+            np.testing.assert_array_equal(eng.alignment_matrix(i), Ms[i])
+    finally:
+        eng.set_alignment_heads(None)
+    eng.align([awin(0, wins[0], z["language"])])
+    np.testing.assert_array_equal(eng.alignment_matrix(0), Ms[0])
+
+
+def test_tiny_decode_undisturbed_by_align(tiny):
+    d, eng, z, wins = tiny
+    sup = get_suppressed_tokens(WhisperTokenizer(d.n_vocab), [-1])
+    cfg = DecodeConfig(suppress_tokens=sup, max_length=64)
+    eng.encode([(0, 0, 3000)])
+    before = eng.decode(1, cfg)[0]
+    eng.align([awin(0, wins[0], z["language"])])
+    after = eng.decode(1, cfg)[0]
+    assert after.tokens == before.tokens
+    assert after.sum_logprob == before.sum_logprob
+    assert after.tokens == np.load(os.path.join(GOLD, "tiny_model.npz"))["ids"][:len(after.tokens)].tolist()
+
+
+def test_align_argument_errors(tiny):
+    from open_speech_amd._lib import OswError
+    d, eng, z, wins = tiny
+    eng.encode([(0, 0, 3000)])
+    with pytest.raises(OswError):   # stale window index
+        eng.align([awin(1, wins[1], z["language"])])
+    with pytest.raises(OswError):   # n + 5 > n_text_ctx
+        eng.align([awin(0, wins[0], z["language"], tokens=[1] * (d.n_text_ctx - 4))])
+    eng.session_begin(DecodeConfig())
+    try:
+        with pytest.raises(OswError):
+            eng.align([awin(0, wins[0], z["language"])])
+    finally:
+        eng.session_end()
+
+
+def test_turbo_matrix_path_and_probs():
+    d = D.LARGE_V3_TURBO
+    z, wins = load_gold("align_turbo.npz")
+    eng = WhisperEngine(d, device=0, max_batch=1)
+    try:
+        eng.init_random(seed=0)
+        eng.log_mel([synth.chirp_clip(0, 30.0)])
+        eng.encode([(0, 0, 3000)])
+        al = eng.align([awin(0, wins[0], z["language"])])[0]
+        check_window(eng, wins[0], al, eng.alignment_matrix(0))
+        check_probs(wins[0], al)
+    finally:
+        eng.close()
+
+
+def test_backend_word_timestamps_end_to_end(monkeypatch, tmp_path):
+    """HipWhisperBackend.transcribe(..., word_timestamps=True) on a transformers-layout model
+    directory (tests/tokfix.py) at micro dims: words on every segment, and the same request
+    without the flag returns exactly what it returns today."""
+    import tokfix
+    from open_speech_amd.backend import HipWhisperBackend
+    from open_speech_amd.segments import verbose_dict  # noqa: F401
+
+    mid = tokfix.make_hf_model_dir(str(tmp_path / "micro_hf"), D.MICRO_TEST)
+    monkeypatch.setenv("STT_HIP_BEAM_SIZE", "1")
+    monkeypatch.setenv("STT_HIP_MAX_BATCH", "2")
+    monkeypatch.setenv("STT_HIP_GPUS", "0")
+    monkeypatch.setenv("STT_HIP_LANES", "1")
+    monkeypatch.delenv("STT_HIP_WORD_TIMESTAMPS", raising=False)
+    b = HipWhisperBackend()
+    b.load_model(mid)
+    try:
+        wav = synth.to_wav_bytes(synth.chirp_clip(41, 40.0))
+        plain = b.transcribe(wav, mid, response_format="verbose_json")
+        r = b.transcribe(wav, mid, response_format="verbose_json", word_timestamps=True)
+        g = b.transcribe(wav, mid, response_format="verbose_json", timestamp_granularities=["word"])
+        again = b.transcribe(wav, mid, response_format="verbose_json", word_timestamps=False)
+    finally:
+        b.unload_model(mid)
+    assert "words" not in plain and all("words" not in s for s in plain["segments"])
+    assert again == plain
+    assert r["segments"] and g == r
+    starts = []
+    for s in r["segments"]:
+        assert s["words"], s
+        assert "".join(w["word"] for w in s["words"]) == s["text"]
+        for w in s["words"]:
+            assert set(w) == {"start", "end", "word", "probability"} and 0.0 <= w["probability"] <= 1.0
+            starts.append(w["start"])
+    assert starts == sorted(starts)
+    assert r["words"] == [{"word": w["word"], "start": w["start"], "end": w["end"]}
+                          for s in r["segments"] for w in s["words"]]
