@@ -36,6 +36,11 @@
  *                 transcribe without it (src/backends/faster_whisper.py:235-246)
  *   osw_get_alignment_matrix / osw_debug_dtw
  *       stage-level read-back and the DTW kernel alone, used only by the parity tests
+ *   osw_decode_opts::repetition_penalty / no_repeat_ngram_size (+ osw_debug_history_rules)
+ *       replace   WhisperModel.transcribe(..., repetition_penalty=, no_repeat_ngram_size=):
+ *                 ctranslate2's RepetitionPenalty / NoRepeatNgram logits processors [upstream],
+ *                 run per decoder row and step on the GPU; the reference itself passes neither
+ *                 (src/backends/faster_whisper.py:235-246)
  *
  * Conventions: every call returns 0 (OSW_OK) or a negative code; the message of
  * the last failure on the calling thread is osw_last_error().  Host buffers are
@@ -132,6 +137,20 @@ typedef struct osw_decode_opts {
      * treats that step as the last one (<= 0: no limit).  NULL: off.  Not a reference
      * option. */
     const int32_t* token_budget;
+    /* history rules = faster-whisper's transcribe(repetition_penalty=, no_repeat_ngram_size=),
+     * i.e. CTranslate2's RepetitionPenalty and NoRepeatNgram logits processors [upstream; the
+     * reference calls transcribe with neither, src/backends/faster_whisper.py:235-246].  A
+     * decoder row's history is what it sampled so far in this window (timestamps included,
+     * the prompt and the previous-text prefix excluded; a beam row: its own hypothesis).  On
+     * every sampled step, on the raw fp32 logits and before every other rule:
+     *   repetition_penalty p: x[t] = x[t] < 0 ? x[t] * p : x[t] / p for every distinct id t of
+     *     the history (<= 0 or == 1: off, so a zeroed struct is off);
+     *   no_repeat_ngram_size m: an id that would complete an m-gram the history already holds
+     *     gets -inf (<= 0: off; 1 bans every id sampled so far).
+     * sum_logprob and the beam scores come from the penalised distribution, as CTranslate2's
+     * do; language detection and no_speech_prob stay on the raw logits. */
+    float repetition_penalty;
+    int32_t no_repeat_ngram_size;
 } osw_decode_opts;
 
 /* Caller-allocated outputs for n windows. */
@@ -311,6 +330,20 @@ int osw_get_alignment_matrix(osw_ctx* ctx, int32_t window, float* out, int64_t o
  * openai-whisper timing.dtw / transformers' _dynamic_time_warping for the parity tests. */
 int osw_debug_dtw(osw_ctx* ctx, const float* x, int32_t T, int32_t F, int32_t* text_idx, int32_t* time_idx,
                   int32_t* len);
+
+/* The history-rules kernel alone (osw_decode_opts::repetition_penalty / no_repeat_ngram_size) on
+ * host data: logits [rows][V] in and out, row r's history tokens[r * stride .. + n_hist[r]).
+ * Replaces CTranslate2's RepetitionPenalty / NoRepeatNgram (transformers'
+ * RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor) for the parity tests.
+ * OSW_EINVAL for n_hist[r] > stride, stride > n_text_ctx, or a token outside [0, V). */
+int osw_debug_history_rules(osw_ctx* ctx, float* logits, int32_t rows, int32_t V, const int32_t* tokens,
+                            int32_t stride, const int32_t* n_hist, float repetition_penalty,
+                            int32_t no_repeat_ngram_size);
+/* Timing helper (tools/history_rules_bench.py): the same kernel on `rows` rows of V zero logits,
+ * every row with a period-3 history of n_hist tokens, launched `iters` times back to back;
+ * *us = mean time per launch (HIP events).  OSW_EINVAL with both rules off. */
+int osw_debug_history_rules_time(osw_ctx* ctx, int32_t rows, int32_t V, int32_t n_hist, float repetition_penalty,
+                                 int32_t no_repeat_ngram_size, int32_t iters, float* us);
 
 /* Parity helper: one encoder block on x [T][D] fp32 (host), result to y (host). */
 int osw_encoder_layer_debug(osw_ctx* ctx, int32_t layer, const float* x, float* y, int32_t T);

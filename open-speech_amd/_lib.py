@@ -35,7 +35,8 @@ class osw_decode_opts(C.Structure):
                 ("language_tokens", C.POINTER(C.c_int32)),
                 ("beam_size", C.c_int32), ("patience", C.c_float), ("length_penalty", C.c_float),
                 ("num_hypotheses", C.c_int32), ("temperature", C.c_float), ("best_of", C.c_int32),
-                ("seed", C.c_uint64), ("token_budget", C.POINTER(C.c_int32))]
+                ("seed", C.c_uint64), ("token_budget", C.POINTER(C.c_int32)),
+                ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32)]
 
 
 class osw_window_result(C.Structure):
@@ -108,6 +109,11 @@ _SIGS = {
                                            P(C.c_int32)]),
     "osw_debug_dtw": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, C.c_int32, P(C.c_int32), P(C.c_int32),
                                 P(C.c_int32)]),
+    # the history-rules kernel alone (replaces ctranslate2's RepetitionPenalty / NoRepeatNgram processors)
+    "osw_debug_history_rules": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, C.c_int32, P(C.c_int32), C.c_int32,
+                                          P(C.c_int32), C.c_float, C.c_int32]),
+    "osw_debug_history_rules_time": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                               C.c_int32, P(C.c_float)]),
     "osw_encoder_layer_debug": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_float), C.c_int32]),
     "osw_debug_gemm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                  P(C.c_float), C.c_int32, P(C.c_float)]),

@@ -261,7 +261,8 @@ class HipWhisperBackend:
     def _run_inference(self, audio: bytes, model_id: str, task: str = "transcribe", language: str | None = None,
                        response_format: str = "json", temperature: float = 0.0,
                        prompt: str | None = None, word_timestamps: bool | None = None,
-                       timestamp_granularities: list | None = None) -> dict[str, Any]:
+                       timestamp_granularities: list | None = None, repetition_penalty: float | None = None,
+                       no_repeat_ngram_size: int | None = None) -> dict[str, Any]:
         m = self._ensure_model(model_id)
         # faster-whisper's word_timestamps=True / OpenAI's timestamp_granularities[]=word; callers
         # that pass neither (the unchanged router) get the STT_HIP_WORD_TIMESTAMPS default
@@ -269,28 +270,40 @@ class HipWhisperBackend:
             words = os.environ.get("STT_HIP_WORD_TIMESTAMPS", "0").lower() in ("1", "true", "yes")
         else:
             words = bool(word_timestamps) or "word" in (timestamp_granularities or ())
+        # faster-whisper's repetition_penalty / no_repeat_ngram_size; callers that pass neither (the
+        # unchanged router) get the STT_HIP_REPETITION_PENALTY / STT_HIP_NO_REPEAT_NGRAM_SIZE defaults
+        if repetition_penalty is None:
+            repetition_penalty = float(os.environ.get("STT_HIP_REPETITION_PENALTY", "1.0"))
+        if no_repeat_ngram_size is None:
+            no_repeat_ngram_size = int(os.environ.get("STT_HIP_NO_REPEAT_NGRAM_SIZE", "0"))
         pcm = decode_audio_bytes(audio)
         opts = TranscribeOptions(task=task, language=language if (language and task == "transcribe") else None,
                                  initial_prompt=prompt or None, temperature=float(temperature or 0.0),
                                  beam_size=int(os.environ.get("STT_HIP_BEAM_SIZE", "5")),
                                  best_of=int(os.environ.get("STT_HIP_BEST_OF", "5")),
-                                 tokens_per_second=self._length_control, word_timestamps=words)
+                                 tokens_per_second=self._length_control, word_timestamps=words,
+                                 repetition_penalty=float(repetition_penalty),
+                                 no_repeat_ngram_size=int(no_repeat_ngram_size))
         res = m.runner.transcribe(pcm, opts)
         return shape_response(task, res, response_format)
 
     def transcribe(self, audio: bytes, model: str, language: str | None = None, response_format: str = "json",
                    temperature: float = 0.0, prompt: str | None = None, word_timestamps: bool | None = None,
-                   timestamp_granularities: list | None = None) -> dict[str, Any]:
+                   timestamp_granularities: list | None = None, repetition_penalty: float | None = None,
+                   no_repeat_ngram_size: int | None = None) -> dict[str, Any]:
         return self._run_inference(audio, model, task="transcribe", language=language,
                                    response_format=response_format, temperature=temperature, prompt=prompt,
-                                   word_timestamps=word_timestamps, timestamp_granularities=timestamp_granularities)
+                                   word_timestamps=word_timestamps, timestamp_granularities=timestamp_granularities,
+                                   repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
 
     def translate(self, audio: bytes, model: str, response_format: str = "json", temperature: float = 0.0,
                   prompt: str | None = None, word_timestamps: bool | None = None,
-                  timestamp_granularities: list | None = None) -> dict[str, Any]:
+                  timestamp_granularities: list | None = None, repetition_penalty: float | None = None,
+                  no_repeat_ngram_size: int | None = None) -> dict[str, Any]:
         return self._run_inference(audio, model, task="translate", response_format=response_format,
                                    temperature=temperature, prompt=prompt, word_timestamps=word_timestamps,
-                                   timestamp_granularities=timestamp_granularities)
+                                   timestamp_granularities=timestamp_granularities,
+                                   repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
 
 
 def _default_engine_factory(dims, gpu: int, max_batch: int):

@@ -80,6 +80,13 @@ void launch_select(const float* logits, int rows, int* pos, const SelParams& P, 
 void launch_beam(const float* logits, int windows, int* pos, const SelParams& P, const unsigned* supmask,
                  SelState* st, const void* sel_parts, void* cand, int* seq, int* anc, int ctx, BeamWin* bw,
                  int* best_tok, int* cur_tok, int max_tokens, int* arrive, hipStream_t s);
+// History rules (osw_decode_opts::repetition_penalty / no_repeat_ngram_size), in place on the raw
+// logits [rows][P.V] before launch_select: one workgroup per decoder row, its history the
+// n_sampled tokens of tokens[row * max_tokens ..] (<= 448).  penalty <= 0 or == 1 and ngram <= 0
+// are "off"; a caller with both off does not launch it (history_rules_on).
+void launch_history_rules(float* logits, int rows, const int* pos, const SelParams& P, const SelState* st,
+                          const int* tokens, int max_tokens, float penalty, int ngram, hipStream_t s);
+inline bool history_rules_on(float penalty, int ngram) { return (penalty > 0.f && penalty != 1.f) || ngram > 0; }
 int sel_parts_bytes();
 int sel_fused_parts_bytes(int V);  // SelFuse::parts of the batch-1 logits GEMM (one record per 64 columns)
 int beam_cand_bytes(int beam);

@@ -926,6 +926,76 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void s
 }
 
 // ---------------------------------------------------------------------------
+// History rules (CTranslate2 RepetitionPenalty and NoRepeatNgram, as faster-whisper's
+// repetition_penalty / no_repeat_ngram_size pass them): grid rows, 256 threads, in place on
+// the row's raw fp32 logits, before the select kernels read them.  The history h[0 .. n) is
+// what the row sampled so far in this window (tokens[row * max_tokens ..], which beam_update
+// reorders per hypothesis); prompt steps, the <|startoftranscript|> step and finished rows
+// are left alone.
+//   penalty p:  every id t in h: x[t] = x[t] < 0 ? x[t] * p : x[t] / p, once per distinct id:
+//               all entries are gathered before any is stored, so duplicates store the same bits
+//   n-gram m:   every i in [0, n - m] with h[i .. i+m-1) == h[n-m+1 .. n): x[h[i+m-1]] = -inf
+// The penalty's stores are complete before the bans' (a banned id stays -inf).  s_barrier
+// waits for no memory counter, hence the explicit vmcnt(0) before each barrier.
+constexpr int HIST_MAX = 448;
+__global__ __launch_bounds__(256) void history_rules_kernel(float* logits, SelParams P, const int* __restrict__ pos_ptr,
+                                                            const SelState* __restrict__ st,
+                                                            const int* __restrict__ tokens, int max_tokens,
+                                                            float penalty, int ngram) {
+    __shared__ int h[HIST_MAX];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const SelState s = st[b];
+    const int step = pos_ptr[P.pos_row ? b : 0];
+    if (sel_mode(P, step, s) != SEL_SAMPLE) return;
+    const int n = min(s.n_sampled, min(max_tokens, HIST_MAX));
+    if (n <= 0) return;
+    float* x = logits + (int64_t)b * P.V;
+    const int* hist = tokens + (int64_t)b * max_tokens;
+    // this thread's history entries: positions tid and tid + 256 (both < 448); an id outside
+    // the vocabulary (never sampled; the debug entry rejects it) is skipped, not indexed with
+    int t[2];
+    float g[2] = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) t[j] = hist[min(tid + 256 * j, n - 1)];  // (both loads in flight together)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int i = tid + 256 * j;
+        if (i < n) h[i] = t[j];
+        if (i >= n || (unsigned)t[j] >= (unsigned)P.V) t[j] = -1;
+    }
+    const bool pen = penalty > 0.f && penalty != 1.f;
+    if (pen) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) g[j] = t[j] >= 0 ? x[t[j]] : 0.f;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every gather has returned
+    }
+    __syncthreads();
+    if (pen) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            if (t[j] >= 0) x[t[j]] = g[j] < 0.f ? g[j] * penalty : g[j] / penalty;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the penalised values are stored
+        __syncthreads();
+    }
+    const int m = ngram;
+    if (m <= 0 || n < m) return;
+    const int tail = n - m + 1;  // the last m - 1 tokens: h[tail .. n)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int i = tid + 256 * j;
+        if (i > n - m) continue;
+        bool match = true;
+        for (int k = 0; k < m - 1; ++k)
+            if (h[i + k] != h[tail + k]) {
+                match = false;
+                break;
+            }
+        const int ban = h[i + m - 1];
+        if (match && (unsigned)ban < (unsigned)P.V) x[ban] = -INFINITY;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Beam search (restated CTranslate2 BeamSearch, see oracle/decode.py): per row the
 // processed log-probs (rules + log-softmax, timestamp-mass rule) plus the row's
 // cumulative score; per window the top 2*beam candidates over beam x vocab, the
@@ -1492,6 +1562,11 @@ void launch_session_rows(const int* pack, int k, int ps, int group, int pstride,
                          int* cur_tok, int* pos, SelState* st, int* anc, BeamWin* bwin, hipStream_t s) {
     session_rows_kernel<<<dim3(k, group), 64, 0, s>>>(pack, ps, group, pstride, ctx, prompt, budget, cur_tok, pos, st,
                                                       anc, bwin);
+}
+
+void launch_history_rules(float* logits, int rows, const int* pos, const SelParams& P, const SelState* st,
+                          const int* tokens, int max_tokens, float penalty, int ngram, hipStream_t s) {
+    history_rules_kernel<<<rows, 256, 0, s>>>(logits, P, pos, st, tokens, max_tokens, penalty, ngram);
 }
 
 void launch_count_done(const SelState* st, int rows, int* out, hipStream_t s) {

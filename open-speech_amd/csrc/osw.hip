@@ -1133,6 +1133,27 @@ hipGraphExec_t decode_graph(osw_ctx* c, const std::vector<int64_t>& key, const s
     }
 }
 
+// osw_decode_opts::repetition_penalty / no_repeat_ngram_size as the decode paths use them:
+// off values normalised (penalty 1, size 0), so equal rules give equal decode-graph keys.
+struct HistRules {
+    bool on;
+    float penalty;
+    int ngram;
+    int32_t penalty_bits() const {
+        int32_t b;
+        std::memcpy(&b, &penalty, 4);
+        return b;
+    }
+};
+HistRules hist_rules(const osw_decode_opts* o, const osw_dims& d) {
+    HistRules h;
+    h.penalty = (o->repetition_penalty > 0.f && o->repetition_penalty != 1.f) ? o->repetition_penalty : 1.f;
+    h.ngram = std::max(0, o->no_repeat_ngram_size);
+    h.on = history_rules_on(h.penalty, h.ngram);
+    REQUIRE(!h.on || d.n_text_ctx <= 448, "the history rules hold at most 448 sampled tokens");
+    return h;
+}
+
 void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r) {
     REQUIRE(nb >= 1 && nb == c->n_encoded, "decode window count must equal the last encode call");
     REQUIRE(o && r && r->tokens && r->n_tokens && r->sum_logprob && r->no_speech_prob && r->language,
@@ -1208,18 +1229,24 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r) 
         HIPCHK(hipMemcpyAsync(c->budget, bud.data(), rows * 4, hipMemcpyHostToDevice, c->stream));
         SP.budget = c->budget;
     }
+    // history rules (repetition_penalty / no_repeat_ngram_size): per row, on the raw logits
+    const HistRules hr = hist_rules(o, d);
     auto select = [&] {
+        if (hr.on)
+            launch_history_rules(c->logits, rows, c->pos, SP, c->sel, c->tokens, max_tok, hr.penalty, hr.ngram,
+                                 c->stream);
         launch_select(c->logits, rows, c->pos, SP, c->prompt, c->supmask, c->sel, c->cur_tok, c->tokens, max_tok,
                       c->selp, c->sel_arrive, beam == 1, c->bcand, c->stream);
         if (beam > 1)
             launch_beam(c->logits, nb, c->pos, SP, c->supmask, c->sel, c->selp, c->bcand, c->tokens, c->anc,
                         d.n_text_ctx, c->bwin, c->btok, c->cur_tok, max_tok, c->sel_arrive, c->stream);
     };
-    // batch-1 greedy: the selection runs in the logits GEMM's epilogue (SelFuse, decode.h)
+    // batch-1 greedy: the selection runs in the logits GEMM's epilogue (SelFuse, decode.h);
+    // not with a history rule on, which has to see the whole row before the selection
     static const bool no_fuse_sel = getenv("OSW_NO_FUSE_SELECT") != nullptr;  // A/B switch
     SelFuse sf{SP, c->logits, c->pos, c->supmask, c->prompt, c->sel, c->cur_tok, c->tokens, max_tok, c->selp1,
                c->sel_arrive + 1};
-    const SelFuse* sfp = (rows == 1 && beam == 1 && !sampling && !no_fuse_sel) ? &sf : nullptr;
+    const SelFuse* sfp = (rows == 1 && beam == 1 && !sampling && !no_fuse_sel && !hr.on) ? &sf : nullptr;
     auto one_step = [&] {
         // the select kernel (greedy), the beam update or the fused selection advances the step counter
         if (!decoder_step(c, rows, group, beam > 1, sfp)) select();
@@ -1233,7 +1260,8 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r) 
         std::vector<int64_t> key = {nb, P, n_pre, max_len, o->eot, o->no_speech, o->no_timestamps,
                                     o->timestamp_begin, o->blank, o->first_lang, o->n_langs, o->suppress_blank,
                                     o->without_timestamps, o->max_initial_timestamp_index, beam, SP.num_hyp,
-                                    SP.max_cand, lp_bits, group, it_bits, SP.budget ? 1 : 0};
+                                    SP.max_cand, lp_bits, group, it_bits, SP.budget ? 1 : 0, hr.penalty_bits(),
+                                    hr.ngram};
         c->dgraph = decode_graph(c, key, one_step, CH);
     }
     int steps = 0;
@@ -1555,6 +1583,7 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
     SP.seed = c->seed_d;
     SP.budget = o->token_budget ? c->budget : nullptr;
     SP.pos_row = 1;
+    const HistRules hr = hist_rules(o, d);
     HIPCHK(hipMemcpyAsync(c->supmask, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, c->stream));
     // every row starts finished (nothing to step until a window is admitted)
     std::vector<SelState> st(R);
@@ -1570,6 +1599,8 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
     c->row_pos = true;
     auto one_step = [&] {
         decoder_step(c, R, 1, false, nullptr);
+        if (hr.on)
+            launch_history_rules(c->logits, R, c->pos, SP, c->sel, c->tokens, max_tok, hr.penalty, hr.ngram, c->stream);
         launch_select(c->logits, R, c->pos, SP, c->prompt, c->supmask, c->sel, c->cur_tok, c->tokens, max_tok,
                       c->selp, c->sel_arrive, true, c->bcand, c->stream);
     };
@@ -1583,7 +1614,7 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
         const std::vector<int64_t> key = {R, P, 0, max_len, o->eot, o->no_speech, o->no_timestamps,
                                           o->timestamp_begin, o->blank, o->first_lang, o->n_langs, o->suppress_blank,
                                           o->without_timestamps, o->max_initial_timestamp_index, 1, 1,
-                                          1, lp_bits, 1, 0, SP.budget ? 1 : 0, -1};
+                                          1, lp_bits, 1, 0, SP.budget ? 1 : 0, -1, hr.penalty_bits(), hr.ngram};
         ge = decode_graph(c, key, one_step, CH);
     }
     std::vector<int> row_clip(R, -1), pack, toks((size_t)R * max_tok);
@@ -1858,6 +1889,7 @@ struct ClipStore {
 struct Session {
     osw_decode_opts o{};
     SelParams SP{};
+    HistRules hr{};  // session-wide repetition_penalty / no_repeat_ngram_size
     int beam = 1, W = 0, tail = 3, max_len = 448, max_tok = 445, ctx = 448;
     std::vector<int64_t> slot_tag;
     std::deque<SessionWin> queue;
@@ -1993,6 +2025,7 @@ void session_begin(osw_ctx* c, const osw_decode_opts* o) {
     REQUIRE(V <= SEL_SPLIT * 4096, "vocabulary too large for the selection kernels");
     auto S = std::make_unique<Session>();
     S->o = *o;
+    S->hr = hist_rules(o, d);
     S->beam = std::max(1, o->beam_size);
     REQUIRE(S->beam <= 5, "decode sessions hold beam_size <= 5 (5 decoder rows per window slot)");
     S->W = c->B;
@@ -2211,6 +2244,9 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
         const SelParams& SP = S->SP;
         auto one_step = [&] {
             decoder_step(c, nb, beam, beam > 1, nullptr);
+            if (S->hr.on)
+                launch_history_rules(c->logits, nb, c->pos, SP, c->sel, c->tokens, S->max_tok, S->hr.penalty,
+                                     S->hr.ngram, c->stream);
             launch_select(c->logits, nb, c->pos, SP, c->prompt, c->supmask, c->sel, c->cur_tok, c->tokens, S->max_tok,
                           c->selp, c->sel_arrive, beam == 1, c->bcand, c->stream);
             if (beam > 1)
@@ -2225,7 +2261,7 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
                                               S->o.timestamp_begin, S->o.blank, S->o.first_lang, S->o.n_langs,
                                               S->o.suppress_blank, S->o.without_timestamps,
                                               S->o.max_initial_timestamp_index, beam, SP.num_hyp, SP.max_cand, lp_bits,
-                                              beam, 0, 1, -2, CH};
+                                              beam, 0, 1, -2, CH, S->hr.penalty_bits(), S->hr.ngram};
             hipGraphExec_t ge = decode_graph(c, key, one_step, CH);
             trace_graph(c, "launch");
             HIPCHK(hipGraphLaunch(ge, c->stream));
@@ -2636,6 +2672,109 @@ int osw_debug_dtw(osw_ctx* c, const float* x, int32_t T, int32_t F, int32_t* tex
             text_idx[i] = back[3 + pcap - k + i];
             time_idx[i] = back[3 + pcap + pcap - k + i];
         }
+    });
+}
+
+int osw_debug_history_rules(osw_ctx* c, float* logits, int32_t rows, int32_t V, const int32_t* tokens, int32_t stride,
+                            const int32_t* n_hist, float repetition_penalty, int32_t no_repeat_ngram_size) {
+    return guard([&] {
+        REQUIRE(c && logits && tokens && n_hist, "null argument");
+        REQUIRE(rows >= 1 && rows <= 65535 && V >= 1 && stride >= 1, "history rules shape out of range");
+        REQUIRE(stride <= c->d.n_text_ctx && stride <= 448, "history stride exceeds n_text_ctx");
+        for (int r = 0; r < rows; ++r) {
+            REQUIRE(n_hist[r] >= 0 && n_hist[r] <= stride, "history longer than its stride");
+            for (int i = 0; i < n_hist[r]; ++i)
+                REQUIRE(tokens[(size_t)r * stride + i] >= 0 && tokens[(size_t)r * stride + i] < V,
+                        "history token outside the vocabulary");
+        }
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        // every row samples at step 0 of a one-token prompt with n_hist[r] tokens behind it
+        SelParams SP{};
+        SP.prompt_len = 1;
+        SP.V = V;
+        std::vector<SelState> st(rows);
+        for (int r = 0; r < rows; ++r) {
+            st[r] = SelState{};
+            st[r].n_sampled = n_hist[r];
+        }
+        std::vector<void*> tmp;
+        float* xd = dalloc<float>((size_t)rows * V, tmp);
+        int* td = dalloc<int>((size_t)rows * stride + 1, tmp);  // histories, then the step counter
+        SelState* sd = dalloc<SelState>((size_t)rows, tmp);
+        const int zero = 0;
+        hipError_t e = hipMemcpyAsync(xd, logits, (size_t)rows * V * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(td, tokens, (size_t)rows * stride * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(td + (size_t)rows * stride, &zero, 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(sd, st.data(), (size_t)rows * sizeof(SelState), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && history_rules_on(repetition_penalty, no_repeat_ngram_size)) {
+            launch_history_rules(xd, rows, td + (size_t)rows * stride, SP, sd, td, stride, repetition_penalty,
+                                 no_repeat_ngram_size, c->stream);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(logits, xd, (size_t)rows * V * 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        dfree(xd, tmp);
+        dfree(td, tmp);
+        dfree(sd, tmp);
+        HIPCHK(e);
+    });
+}
+
+int osw_debug_history_rules_time(osw_ctx* c, int32_t rows, int32_t V, int32_t n_hist, float repetition_penalty,
+                                 int32_t no_repeat_ngram_size, int32_t iters, float* us) {
+    return guard([&] {
+        REQUIRE(c && us, "null argument");
+        REQUIRE(rows >= 1 && rows <= 65535 && V >= 4 && iters >= 1, "history rules shape out of range");
+        REQUIRE(n_hist >= 0 && n_hist <= c->d.n_text_ctx && n_hist <= 448, "history longer than n_text_ctx");
+        REQUIRE(history_rules_on(repetition_penalty, no_repeat_ngram_size), "both rules are off: nothing to time");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        const int stride = std::max(1, (int)n_hist);
+        SelParams SP{};
+        SP.prompt_len = 1;
+        SP.V = V;
+        std::vector<SelState> st(rows);
+        for (auto& q : st) q = SelState{}, q.n_sampled = n_hist;
+        std::vector<int> hist((size_t)rows * stride + 1, 0);  // period 3 (every thread's prefix matches), then the step counter
+        for (int r = 0; r < rows; ++r)
+            for (int i = 0; i < stride; ++i) hist[(size_t)r * stride + i] = 1 + i % 3;
+        std::vector<void*> tmp;
+        float* xd = dalloc<float>((size_t)rows * V, tmp);
+        int* td = dalloc<int>(hist.size(), tmp);
+        SelState* sd = dalloc<SelState>((size_t)rows, tmp);
+        hipEvent_t e0, e1;
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        try {
+            HIPCHK(hipMemsetAsync(xd, 0, (size_t)rows * V * 4, c->stream));
+            HIPCHK(hipMemcpyAsync(td, hist.data(), hist.size() * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(sd, st.data(), (size_t)rows * sizeof(SelState), hipMemcpyHostToDevice, c->stream));
+            auto run = [&] {
+                launch_history_rules(xd, rows, td + (size_t)rows * stride, SP, sd, td, stride, repetition_penalty,
+                                     no_repeat_ngram_size, c->stream);
+            };
+            run();  // warm
+            HIPCHK(hipEventRecord(e0, c->stream));
+            for (int i = 0; i < iters; ++i) run();
+            HIPCHK(hipEventRecord(e1, c->stream));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventSynchronize(e1));
+            float t = 0.f;
+            HIPCHK(hipEventElapsedTime(&t, e0, e1));
+            *us = t * 1e3f / iters;
+        } catch (...) {
+            (void)hipEventDestroy(e0);
+            (void)hipEventDestroy(e1);
+            for (void* p : tmp) (void)hipFree(p);
+            throw;
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        for (void* p : tmp) (void)hipFree(p);
     });
 }
 

@@ -37,6 +37,10 @@ class DecodeConfig:
     # length control (bench only; not a faster-whisper option): window i ends with
     # <|endoftext|> after token_budget[i] sampled tokens (<= 0: no limit)
     token_budget: tuple | None = None
+    # faster-whisper's repetition_penalty / no_repeat_ngram_size (CTranslate2 logits processors)
+    # over what the row sampled so far in its window: 1.0 / 0 = off
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
 
 
 @dataclass
@@ -209,7 +213,8 @@ class WhisperEngine:
             timestamp_begin=st.timestamp_begin, blank=st.blank, first_lang=st.first_lang, n_langs=st.n_langs,
             prefix_tokens=_i32p(pre), n_prefix=n_pre, beam_size=int(cfg.beam_size), patience=float(cfg.patience),
             length_penalty=float(cfg.length_penalty), num_hypotheses=int(cfg.num_hypotheses),
-            temperature=float(cfg.temperature), best_of=int(cfg.best_of), seed=int(cfg.seed) & 0xFFFFFFFFFFFFFFFF)
+            temperature=float(cfg.temperature), best_of=int(cfg.best_of), seed=int(cfg.seed) & 0xFFFFFFFFFFFFFFFF,
+            repetition_penalty=float(cfg.repetition_penalty), no_repeat_ngram_size=int(cfg.no_repeat_ngram_size))
         budget = None
         if cfg.token_budget is not None:
             if len(cfg.token_budget) != n:
@@ -409,6 +414,31 @@ class WhisperEngine:
         _lib.check(self.lib.osw_debug_dtw(self.ctx, x.ctypes.data_as(C.POINTER(C.c_float)), T, F, _i32p(ti),
                                           _i32p(fi), C.byref(n)), "osw_debug_dtw")
         return ti[:n.value].copy(), fi[:n.value].copy()
+
+    def debug_history_rules(self, logits: np.ndarray, tokens: np.ndarray, n_hist, repetition_penalty: float = 1.0,
+                            no_repeat_ngram_size: int = 0) -> np.ndarray:
+        """The history-rules kernel alone: logits [rows][V] with row r's history
+        ``tokens[r, :n_hist[r]]``; returns the processed logits (the input is not changed)."""
+        x = np.array(logits, dtype=np.float32, order="C", ndmin=2)
+        t = np.ascontiguousarray(np.atleast_2d(tokens), dtype=np.int32)
+        n = np.ascontiguousarray(n_hist, dtype=np.int32).reshape(-1)
+        if t.shape[0] != x.shape[0] or n.shape[0] != x.shape[0]:
+            raise ValueError("one history and one length per logits row")
+        _lib.check(self.lib.osw_debug_history_rules(self.ctx, x.ctypes.data_as(C.POINTER(C.c_float)), x.shape[0],
+                                                    x.shape[1], _i32p(t), t.shape[1], _i32p(n),
+                                                    float(repetition_penalty), int(no_repeat_ngram_size)),
+                   "osw_debug_history_rules")
+        return x
+
+    def debug_history_rules_time(self, rows: int, n_hist: int, repetition_penalty: float = 1.0,
+                                 no_repeat_ngram_size: int = 0, iters: int = 200) -> float:
+        """Mean microseconds per launch of the history-rules kernel on ``rows`` rows of the
+        model's vocabulary, each with ``n_hist`` tokens of history (HIP events)."""
+        us = C.c_float()
+        _lib.check(self.lib.osw_debug_history_rules_time(self.ctx, int(rows), self.dims.n_vocab, int(n_hist),
+                                                         float(repetition_penalty), int(no_repeat_ngram_size),
+                                                         int(iters), C.byref(us)), "osw_debug_history_rules_time")
+        return us.value
 
     def debug_gemm(self, A: np.ndarray, W: np.ndarray, variant: int = 0, iters: int = 1):
         """C = A·Wᵀ (fp16 in, fp32 out) through one GEMM kernel variant; returns (C, mean ms)."""

@@ -70,12 +70,23 @@ class TranscribeOptions:
     word_timestamps: bool = False
     prepend_punctuations: str = "\"'“¿([{-"
     append_punctuations: str = "\"'.。,，!！?？:：”)]}、"
+    # faster-whisper's repetition_penalty / no_repeat_ngram_size (CTranslate2's constraints:
+    # penalty > 0, size >= 0); 1.0 / 0 = off
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+
+    def __post_init__(self):
+        if not float(self.repetition_penalty) > 0:
+            raise ValueError(f"repetition_penalty must be > 0, got {self.repetition_penalty!r}")
+        if int(self.no_repeat_ngram_size) < 0:
+            raise ValueError(f"no_repeat_ngram_size must be >= 0, got {self.no_repeat_ngram_size!r}")
 
     def key(self):
         return (self.task, self.language, self.initial_prompt, self.condition_on_previous_text,
                 self.without_timestamps, tuple(self.suppress_tokens), self.suppress_blank, self.beam_size,
                 self.patience, self.length_penalty, self.temperature, self.best_of, self.tokens_per_second,
-                self.max_new_tokens, self.word_timestamps, self.prepend_punctuations, self.append_punctuations)
+                self.max_new_tokens, self.word_timestamps, self.prepend_punctuations, self.append_punctuations,
+                float(self.repetition_penalty), int(self.no_repeat_ngram_size))
 
 
 @dataclass
@@ -203,7 +214,9 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
                                    suppress_blank=opts.suppress_blank, without_timestamps=opts.without_timestamps,
                                    max_initial_timestamp_index=max_init, beam_size=beam, patience=opts.patience,
                                    length_penalty=opts.length_penalty, temperature=opts.temperature,
-                                   best_of=opts.best_of, seed=(opts.seed + 0x9E3779B1 * calls) & (2**64 - 1))
+                                   best_of=opts.best_of, seed=(opts.seed + 0x9E3779B1 * calls) & (2**64 - 1),
+                                   repetition_penalty=float(opts.repetition_penalty),
+                                   no_repeat_ngram_size=int(opts.no_repeat_ngram_size))
                 if opts.tokens_per_second:
                     cfg.token_budget = tuple(int(np.ceil(opts.tokens_per_second * z * FRAME_SEC)) + 2
                                              for _, _, z in wins)
@@ -255,7 +268,8 @@ def session_config(opts: TranscribeOptions, suppress: tuple) -> DecodeConfig:
                         suppress_blank=opts.suppress_blank, without_timestamps=opts.without_timestamps,
                         max_initial_timestamp_index=int(round(opts.max_initial_timestamp / TIME_PRECISION)),
                         beam_size=max(1, int(opts.beam_size)), patience=opts.patience,
-                        length_penalty=opts.length_penalty)
+                        length_penalty=opts.length_penalty, repetition_penalty=float(opts.repetition_penalty),
+                        no_repeat_ngram_size=int(opts.no_repeat_ngram_size))
 
 
 def clip_state(idx: int, pcm: np.ndarray, opts: TranscribeOptions, tok: WhisperTokenizer) -> _ClipState:
