@@ -41,6 +41,12 @@
  *                 ctranslate2's RepetitionPenalty / NoRepeatNgram logits processors [upstream],
  *                 run per decoder row and step on the GPU; the reference itself passes neither
  *                 (src/backends/faster_whisper.py:235-246)
+ *   osw_set_confidences / osw_get_token_logprobs / osw_get_language_probs / osw_detect_language
+ *       replace   the per-token log-probabilities a CTranslate2 WhisperGenerationResult can
+ *                 return (return_scores / return_logits_vocab) [upstream], TranscriptionInfo's
+ *                 language_probability / all_language_probs and WhisperModel.detect_language()
+ *                 -> ctranslate2 Whisper.detect_language(encoder_output) [upstream]; the reference
+ *                 reads none of them and hard-codes its confidences (src/streaming.py:407,419)
  *
  * Conventions: every call returns 0 (OSW_OK) or a negative code; the message of
  * the last failure on the calling thread is osw_last_error().  Host buffers are
@@ -245,7 +251,7 @@ int osw_transcribe_refill(osw_ctx* ctx, const int16_t* pcm, const int64_t* offse
 /* ---- decode sessions: continuous batching of windows (greedy or beam search) ----
  * A session keeps max_batch window slots on the context (beam search: beam_size decoder
  * rows per slot, each with its own step counter and prompt).  Windows are queued with
- * osw_session_add and admitted into free slots between chunks of 8 decoder steps (their
+ * osw_session_add and admitted into free slots between chunks of 4 decoder steps (their
  * encoder runs straight into the slot's cross-K/V); a finished window leaves its slot at
  * once.  So a window queued while others decode joins at the next chunk instead of
  * waiting for the longest window of a batch, and a caller can queue the next window of a
@@ -288,6 +294,40 @@ int osw_session_step(osw_ctx* ctx, int32_t max_chunks, int32_t refill_min, osw_w
  * already admitted were staged and are unaffected). */
 int osw_session_release_clip(osw_ctx* ctx, int64_t clip);
 int osw_session_end(osw_ctx* ctx);
+
+/* ---- confidences: per-token log-probabilities and language probabilities ----
+ * Off by default.  On, every decode entry point (osw_decode_windows, osw_transcribe_batch,
+ * osw_transcribe_refill, osw_session_step) also keeps, per returned window, what the token
+ * selection computes anyway: the row's cumulative log-probability after each sampled step and
+ * the softmax over the language tokens' raw <|startoftranscript|> logits.  Tokens, sum_logprob,
+ * no_speech_prob and language are the same bits on and off.  Replaces the scores CTranslate2's
+ * Whisper.generate(return_scores=True) returns per hypothesis, refined to one value per token
+ * (OpenAI's include[]=logprobs), and faster-whisper's TranscriptionInfo.language_probability /
+ * all_language_probs [upstream]; the reference reads neither (src/backends/faster_whisper.py:
+ * 235-260).  OSW_EINVAL while a session is open (a session keeps the setting it began with). */
+int osw_set_confidences(osw_ctx* ctx, int32_t enable);
+/* Result i of the last result-producing call on this context (window i of osw_decode_windows /
+ * osw_transcribe_batch, clip i of osw_transcribe_refill, entry i of the last osw_session_step's
+ * done-list; sampling: the best_of row that was returned).  cum[j] = the fp32 cumulative
+ * log-probability after token j; *n = the window's n_tokens, plus one closing entry when the row
+ * ended with an <|endoftext|> step (picked, or forced by its token budget), none when it was cut
+ * at max_length.  The last entry equals the window's sum_logprob bit for bit; token j's own
+ * log-probability is cum[j] - cum[j - 1] (the caller subtracts, in double).  cum may be NULL to
+ * query *n.  OSW_ESTATE with confidences off or before any such call. */
+int osw_get_token_logprobs(osw_ctx* ctx, int32_t i, float* cum, int32_t cap, int32_t* n);
+/* probs[n_langs] of the same result i: softmax over logits[first_lang .. first_lang + n_langs) at
+ * the <|startoftranscript|> step (CTranslate2 detect_language's distribution), whether the
+ * language was detected or given.  n_langs must be the decode call's.  OSW_ESTATE as above. */
+int osw_get_language_probs(osw_ctx* ctx, int32_t i, float* probs, int32_t n_langs);
+/* Language detection alone for the n windows of the last osw_encode_windows call: one decoder
+ * step on <|startoftranscript|> (no prefix), then the same language softmax; probs [n][n_langs],
+ * raw_logits (optional) [n][n_langs] the logits it was taken over.  opts supplies the token ids
+ * only (sot, task_token, first_lang, n_langs).  Needs no osw_set_confidences, touches no result
+ * of an earlier call, and a later osw_decode_windows of the same windows returns what it would
+ * have without it.  Runs on the context's stream and allocates nothing.  Replaces
+ * WhisperModel.detect_language() -> ctranslate2 Whisper.detect_language [upstream].  OSW_EINVAL
+ * while a session is open. */
+int osw_detect_language(osw_ctx* ctx, int32_t n, const osw_decode_opts* opts, float* probs, float* raw_logits);
 
 /* ---- word timestamps: cross-attention alignment + dynamic time warping ----
  * The alignment heads as n (layer, head) pairs (an HF generation_config.json's

@@ -102,6 +102,12 @@ _SIGS = {
                                    P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
     "osw_session_release_clip": (C.c_int, [C.c_void_p, C.c_int64]),
     "osw_session_end": (C.c_int, [C.c_void_p]),
+    # confidences (replace ctranslate2's return_scores per token, faster-whisper's language_probability /
+    # all_language_probs and WhisperModel.detect_language)
+    "osw_set_confidences": (C.c_int, [C.c_void_p, C.c_int32]),
+    "osw_get_token_logprobs": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), C.c_int32, P(C.c_int32)]),
+    "osw_get_language_probs": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), C.c_int32]),
+    "osw_detect_language": (C.c_int, [C.c_void_p, C.c_int32, P(osw_decode_opts), P(C.c_float), P(C.c_float)]),
     # word timestamps (replace ctranslate2 Whisper.align as faster-whisper's find_alignment calls it)
     "osw_set_alignment_heads": (C.c_int, [C.c_void_p, P(C.c_int32), C.c_int32]),
     "osw_align_windows": (C.c_int, [C.c_void_p, C.c_int32, P(osw_align_window), P(osw_align_result)]),

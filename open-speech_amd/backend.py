@@ -262,8 +262,14 @@ class HipWhisperBackend:
                        response_format: str = "json", temperature: float = 0.0,
                        prompt: str | None = None, word_timestamps: bool | None = None,
                        timestamp_granularities: list | None = None, repetition_penalty: float | None = None,
-                       no_repeat_ngram_size: int | None = None) -> dict[str, Any]:
+                       no_repeat_ngram_size: int | None = None, include: list | None = None) -> dict[str, Any]:
         m = self._ensure_model(model_id)
+        # OpenAI's include[]=logprobs; callers that pass nothing (the unchanged router) get the
+        # STT_HIP_LOGPROBS default
+        if include is None:
+            logprobs = os.environ.get("STT_HIP_LOGPROBS", "0").lower() in ("1", "true", "yes")
+        else:
+            logprobs = "logprobs" in include
         # faster-whisper's word_timestamps=True / OpenAI's timestamp_granularities[]=word; callers
         # that pass neither (the unchanged router) get the STT_HIP_WORD_TIMESTAMPS default
         if word_timestamps is None and timestamp_granularities is None:
@@ -283,15 +289,24 @@ class HipWhisperBackend:
                                  best_of=int(os.environ.get("STT_HIP_BEST_OF", "5")),
                                  tokens_per_second=self._length_control, word_timestamps=words,
                                  repetition_penalty=float(repetition_penalty),
-                                 no_repeat_ngram_size=int(no_repeat_ngram_size))
+                                 no_repeat_ngram_size=int(no_repeat_ngram_size), token_logprobs=logprobs)
         res = m.runner.transcribe(pcm, opts)
-        return shape_response(task, res, response_format)
+        return shape_response(task, res, response_format, m.tokenizer, logprobs)
+
+    def detect_language(self, audio: bytes, model: str) -> dict[str, Any]:
+        """``WhisperModel.detect_language`` on the first 30 s window (faster-whisper's default
+        language_detection_segments = 1): the language code, its probability and every
+        language's (code, probability) by falling probability."""
+        m = self._ensure_model(model)
+        res = m.runner.transcribe(decode_audio_bytes(audio), TranscribeOptions(detect_only=True))
+        return {"language": res.language, "language_probability": res.language_probability,
+                "all_language_probs": res.all_language_probs}
 
     def transcribe(self, audio: bytes, model: str, language: str | None = None, response_format: str = "json",
                    temperature: float = 0.0, prompt: str | None = None, word_timestamps: bool | None = None,
                    timestamp_granularities: list | None = None, repetition_penalty: float | None = None,
-                   no_repeat_ngram_size: int | None = None) -> dict[str, Any]:
-        return self._run_inference(audio, model, task="transcribe", language=language,
+                   no_repeat_ngram_size: int | None = None, include: list | None = None) -> dict[str, Any]:
+        return self._run_inference(audio, model, task="transcribe", language=language, include=include,
                                    response_format=response_format, temperature=temperature, prompt=prompt,
                                    word_timestamps=word_timestamps, timestamp_granularities=timestamp_granularities,
                                    repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
@@ -299,8 +314,8 @@ class HipWhisperBackend:
     def translate(self, audio: bytes, model: str, response_format: str = "json", temperature: float = 0.0,
                   prompt: str | None = None, word_timestamps: bool | None = None,
                   timestamp_granularities: list | None = None, repetition_penalty: float | None = None,
-                  no_repeat_ngram_size: int | None = None) -> dict[str, Any]:
-        return self._run_inference(audio, model, task="translate", response_format=response_format,
+                  no_repeat_ngram_size: int | None = None, include: list | None = None) -> dict[str, Any]:
+        return self._run_inference(audio, model, task="translate", response_format=response_format, include=include,
                                    temperature=temperature, prompt=prompt, word_timestamps=word_timestamps,
                                    timestamp_granularities=timestamp_granularities,
                                    repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)

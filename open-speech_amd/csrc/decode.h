@@ -11,7 +11,7 @@ struct SelState {
     float sum_lp, nsp;  // greedy: Σ log-prob of the picks; beam: the hypothesis' cumulative score
     int plen;           // this row's prompt length (0: SelParams::prompt_len; decode sessions admit
                         // windows with different previous-text prefixes)
-    int pad;
+    int n_lp;           // confidences on: cumulative log-probs recorded for this row (SelParams::lp_hist)
 };
 
 struct SelParams {
@@ -32,6 +32,14 @@ struct SelParams {
     const int* budget;     // per decoder row: force <|endoftext|> after this many sampled tokens (<= 0: none);
                            // nullptr: no budgets (osw_decode_opts::token_budget, length-controlled benches)
     int pos_row;           // 1: row r's step counter is pos[r] (row refill, sessions), 0: one shared counter
+    // Confidences (osw_set_confidences); every pointer nullptr when off, and nothing is stored.
+    float* lp_hist;        // [rows][lp_stride]: the row's cumulative log-prob after its i-th sampled step (the
+                           // <|endoftext|> step included).  Beam rows: written once at [physical row][i]; a
+                           // hypothesis' entry i lives in the row its ancestry names at position plen + i
+    float* best_lp;        // beam: [windows][lp_stride], the best finished hypothesis' history (beside best_tok)
+    float* lang_probs;     // [windows][n_langs]: softmax over the language tokens' raw <|startoftranscript|> logits
+    int lp_stride;         // floats per row of lp_hist / best_lp (n_text_ctx)
+    int lp_group;          // decoder rows per window (beam_size or best_of): row w * lp_group writes lang_probs[w]
 };
 
 // the row's prompt length and <|startoftranscript|> position
@@ -42,7 +50,8 @@ __host__ __device__ __forceinline__ int row_plen(const SelParams& P, const SelSt
 // Per window in beam mode: finished-hypothesis bookkeeping (the best one's tokens
 // are copied to a per-window buffer when it improves).
 struct BeamWin {
-    int n_hyp, best_len, done, pad;
+    int n_hyp, best_len, done;
+    int best_nlp;  // confidences on: entries of SelParams::best_lp (best_len, + 1 when it ended with <|endoftext|>)
     float best_norm, best_raw;
 };
 

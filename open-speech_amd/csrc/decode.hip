@@ -1060,7 +1060,7 @@ __device__ __forceinline__ void beam_update_body(const SelParams& P, const int* 
     __shared__ int lanc[KM][448];
     __shared__ SelState lst[KM];
     __shared__ int ch_src[KM], ch_tok[KM], fin, best_src, best_extra, improved;
-    __shared__ float ch_score[KM];
+    __shared__ float ch_score[KM], best_score;
     OSW_STAMP(0);
     const int w = blockIdx.x, tid = threadIdx.x, K = P.beam, K2 = 2 * K;
     const int r0 = w * K;
@@ -1278,6 +1278,8 @@ __device__ __forceinline__ void beam_update_body(const SelParams& P, const int* 
                         bw.best_len = min(len, max_tokens);
                         best_src = __builtin_amdgcn_readlane(srcj, k);
                         best_extra = tok == P.eot ? -1 : tok;
+                        best_score = cs[k];
+                        if (P.lp_hist) bw.best_nlp = min(n + 1, P.lp_stride);
                         improved = 1;
                     }
                     // the next continuation at or after position sec replaces it
@@ -1303,6 +1305,17 @@ __device__ __forceinline__ void beam_update_body(const SelParams& P, const int* 
         int* dst = best_tok + (int64_t)w * max_tokens;
         for (int j = tid; j < n && j < max_tokens; j += 256) dst[j] = lseq[best_src][j];
         if (tid == 0 && best_extra >= 0 && n < max_tokens) dst[n] = best_extra;
+        if (P.lp_hist) {
+            // confidences: the winner's cumulative log-probs.  Entry j was stored once, by the row
+            // the hypothesis occupied after sampled step j: the row its ancestry names at position
+            // plen + j (the source row itself for the newest one); this step's score closes it
+            float* dl = P.best_lp + (int64_t)w * P.lp_stride;
+            for (int j = tid; j < n && j < P.lp_stride; j += 256) {
+                const int row = plen + j < step ? lanc[best_src][plen + j] : r0 + best_src;
+                dl[j] = P.lp_hist[(int64_t)row * P.lp_stride + j];
+            }
+            if (tid == 0 && n < P.lp_stride) dl[n] = best_score;
+        }
     }
     if (fin) {
         if (tid < K) {
@@ -1339,6 +1352,7 @@ __device__ __forceinline__ void beam_update_body(const SelParams& P, const int* 
         s2.last = tok;
         if (tok >= P.tb) s2.last_ts = tok;
         s2.sum_lp = ch_score[tid];
+        if (P.lp_hist && n < P.lp_stride) P.lp_hist[(int64_t)(r0 + tid) * P.lp_stride + n] = s2.sum_lp;
         st[r0 + tid] = s2;
         cur_tok[r0 + tid] = tok;
     }

@@ -317,6 +317,17 @@ struct osw_ctx {
     bool prof_eager = false;  // profiling mode 2: decode steps launched eagerly so the per-kernel timers see them
     bool use_graph = true;
 
+    // confidences (osw_set_confidences): per-token cumulative log-probs and language probabilities
+    bool conf = false;
+    float* lp_hist = nullptr;     // [R][n_text_ctx] (SelParams::lp_hist)
+    float* best_lp = nullptr;     // beam: [B][n_text_ctx] (SelParams::best_lp)
+    float* lang_probs = nullptr;  // [B][<= LANG_CAP] (SelParams::lang_probs; osw_detect_language writes it too)
+    struct ConfResult {
+        std::vector<float> cum, lang;
+    };
+    std::vector<ConfResult> conf_res;  // results of the last result-producing call, in its order
+    bool conf_valid = false;
+
     AlignBufs al;
     const AlignCapture* acap = nullptr;  // set while osw_align_windows steps the decoder
 
@@ -329,6 +340,7 @@ struct osw_ctx {
 
 namespace {
 const int T_ENC = 1500;
+const int LANG_CAP = 128;  // language tokens a window's language_probs row holds (Whisper: 99 or 100)
 const int N_FR = 3000;
 
 // OSW_TRACE_GRAPH=1: one stderr line per decode-graph event (capture, instantiate, launch,
@@ -637,6 +649,9 @@ void setup_workspace(osw_ctx* c) {
     c->xticket = dalloc<int>(B * d.n_text_head, o);
     HIPCHK(hipMemsetAsync(c->xticket, 0, (size_t)B * d.n_text_head * sizeof(int), c->stream));
     c->budget = dalloc<int>(R, o);
+    c->lp_hist = dalloc<float>(R * d.n_text_ctx, o);
+    c->best_lp = dalloc<float>(B * d.n_text_ctx, o);
+    c->lang_probs = dalloc<float>(B * LANG_CAP, o);
     c->seed_d = dalloc<unsigned long long>(1, o);
     c->tail_ticket = dalloc<int>(4096, o);  // GEMM tails: [column blocks x row groups] (zero between launches)
     HIPCHK(hipMemsetAsync(c->tail_ticket, 0, 4096 * sizeof(int), c->stream));
@@ -1133,6 +1148,29 @@ hipGraphExec_t decode_graph(osw_ctx* c, const std::vector<int64_t>& key, const s
     }
 }
 
+// Confidences (osw_set_confidences): the recording pointers of a decode's SelParams (all null
+// when off, so the kernels store nothing) ...
+void conf_params(const osw_ctx* c, SelParams& SP, int group) {
+    SP.lp_group = std::max(1, group);
+    SP.lp_stride = c->d.n_text_ctx;
+    if (!c->conf) return;
+    REQUIRE(SP.n_langs >= 1 && SP.n_langs <= LANG_CAP, "confidences hold at most 128 languages");
+    SP.lp_hist = c->lp_hist;
+    SP.best_lp = c->best_lp;
+    SP.lang_probs = c->lang_probs;
+}
+// ... and the read-back of one finished window into conf_res[i]: `cum` = the row's lp_hist (or the
+// window's best_lp), `nlp` its recorded entries, n0 / n the window's token count before / after
+// the caller's max_tokens clamp.  nlp == n0 + 1: the row ended with an <|endoftext|> step, whose
+// entry stays the last one.
+void conf_store(osw_ctx* c, size_t i, const float* cum, int nlp, int n0, int n, const float* lang, int n_langs) {
+    if (c->conf_res.size() <= i) c->conf_res.resize(i + 1);
+    osw_ctx::ConfResult& q = c->conf_res[i];
+    q.cum.assign(cum, cum + std::min(n, nlp));
+    if (nlp == n0 + 1) q.cum.push_back(cum[nlp - 1]);
+    q.lang.assign(lang, lang + n_langs);
+}
+
 // osw_decode_opts::repetition_penalty / no_repeat_ngram_size as the decode paths use them:
 // off values normalised (penalty 1, size 0), so equal rules give equal decode-graph keys.
 struct HistRules {
@@ -1229,6 +1267,8 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r) 
         HIPCHK(hipMemcpyAsync(c->budget, bud.data(), rows * 4, hipMemcpyHostToDevice, c->stream));
         SP.budget = c->budget;
     }
+    c->conf_valid = false;
+    conf_params(c, SP, group);
     // history rules (repetition_penalty / no_repeat_ngram_size): per row, on the raw logits
     const HistRules hr = hist_rules(o, d);
     auto select = [&] {
@@ -1261,7 +1301,7 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r) 
                                     o->timestamp_begin, o->blank, o->first_lang, o->n_langs, o->suppress_blank,
                                     o->without_timestamps, o->max_initial_timestamp_index, beam, SP.num_hyp,
                                     SP.max_cand, lp_bits, group, it_bits, SP.budget ? 1 : 0, hr.penalty_bits(),
-                                    hr.ngram};
+                                    hr.ngram, c->conf ? 1 : 0};
         c->dgraph = decode_graph(c, key, one_step, CH);
     }
     int steps = 0;
@@ -1312,6 +1352,16 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r) 
     } else {
         HIPCHK(hipMemcpyAsync(toks.data(), c->tokens, toks.size() * 4, hipMemcpyDeviceToHost, c->stream));
     }
+    const int ctx = d.n_text_ctx;
+    std::vector<float> cum, lang;
+    if (c->conf) {
+        cum.resize((size_t)(beam > 1 ? nb : rows) * ctx);
+        lang.resize((size_t)nb * o->n_langs);
+        HIPCHK(hipMemcpyAsync(cum.data(), beam > 1 ? c->best_lp : c->lp_hist, cum.size() * 4, hipMemcpyDeviceToHost,
+                              c->stream));
+        HIPCHK(hipMemcpyAsync(lang.data(), c->lang_probs, lang.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        c->conf_res.clear();
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     // best_of: the sample with the highest sum_logprob / n**length_penalty (first on ties)
     auto norm = [&](const SelState& q) {
@@ -1332,7 +1382,56 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r) 
         r->sum_logprob[b] = beam > 1 ? bw[b].best_raw : sp.sum_lp;
         r->no_speech_prob[b] = sp.nsp;
         r->language[b] = sp.lang;
+        if (c->conf)
+            conf_store(c, b, &cum[(beam > 1 ? (size_t)b : best) * ctx], beam > 1 ? bw[b].best_nlp : sp.n_lp, n0, n,
+                       &lang[(size_t)b * o->n_langs], o->n_langs);
     }
+    c->conf_valid = c->conf;
+}
+
+// osw_detect_language: one decoder step on <|startoftranscript|> (no prefix) for the n windows
+// last encoded, then the select kernel's <|startoftranscript|> branch with the language softmax
+// on.  Launched eagerly on the context's stream; every buffer it writes (row state, step
+// counter, position 0 of the self-K/V cache) is reset or rewritten by the next decode call, and
+// the encoder output and cross-K/V are only read.
+void detect_language(osw_ctx* c, int nb, const osw_decode_opts* o, float* probs, float* raw) {
+    REQUIRE(nb >= 1 && nb == c->n_encoded, "detect window count must equal the last encode call");
+    REQUIRE(o && probs, "null detect argument");
+    const osw_dims& d = c->d;
+    const int V = d.n_vocab, P = 3;
+    REQUIRE(V <= SEL_SPLIT * 4096, "vocabulary too large for the selection kernels");
+    REQUIRE(o->n_langs >= 1 && o->n_langs <= LANG_CAP && o->first_lang >= 0 && o->first_lang + o->n_langs <= V,
+            "language token range");
+    REQUIRE(nb <= c->R && P < d.n_text_ctx, "decoder rows");
+    std::vector<int> prompt((size_t)nb * P), first(nb, o->sot);
+    for (int b = 0; b < nb; ++b) {
+        prompt[(size_t)b * P] = o->sot;
+        prompt[(size_t)b * P + 1] = -1;
+        prompt[(size_t)b * P + 2] = o->task_token;
+    }
+    HIPCHK(hipMemcpyAsync(c->prompt, prompt.data(), prompt.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->cur_tok, first.data(), (size_t)nb * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(c->pos, 0, 4, c->stream));
+    HIPCHK(hipMemsetAsync(c->sel, 0, (size_t)nb * sizeof(SelState), c->stream));
+    SelParams SP{};
+    SP.prompt_len = P; SP.sot_pos = 0; SP.lang_pos = 1; SP.max_length = d.n_text_ctx;
+    SP.pstride = P; SP.tail = P;
+    SP.V = V; SP.eot = o->eot; SP.no_speech = std::max(0, std::min(o->no_speech, V - 1));
+    SP.no_ts = o->no_timestamps; SP.tb = o->timestamp_begin;
+    SP.blank = o->blank; SP.first_lang = o->first_lang; SP.n_langs = o->n_langs;
+    SP.beam = 1; SP.num_hyp = 1; SP.max_cand = 1;
+    SP.seed = c->seed_d;
+    SP.lp_group = 1; SP.lp_stride = d.n_text_ctx;
+    SP.lang_probs = c->lang_probs;
+    decoder_step(c, nb, 1, false, nullptr);
+    launch_select(c->logits, nb, c->pos, SP, c->prompt, c->supmask, c->sel, c->cur_tok, c->tokens, 1, c->selp,
+                  c->sel_arrive, true, c->bcand, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(probs, c->lang_probs, (size_t)nb * o->n_langs * 4, hipMemcpyDeviceToHost, c->stream));
+    if (raw)
+        HIPCHK(hipMemcpy2DAsync(raw, (size_t)o->n_langs * 4, c->logits + o->first_lang, (size_t)V * 4,
+                                (size_t)o->n_langs * 4, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
 }
 
 // ------------------------------ word-timestamp alignment ------------------------------
@@ -1583,6 +1682,9 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
     SP.seed = c->seed_d;
     SP.budget = o->token_budget ? c->budget : nullptr;
     SP.pos_row = 1;
+    c->conf_valid = false;
+    c->conf_res.clear();
+    conf_params(c, SP, 1);
     const HistRules hr = hist_rules(o, d);
     HIPCHK(hipMemcpyAsync(c->supmask, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, c->stream));
     // every row starts finished (nothing to step until a window is admitted)
@@ -1614,10 +1716,13 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
         const std::vector<int64_t> key = {R, P, 0, max_len, o->eot, o->no_speech, o->no_timestamps,
                                           o->timestamp_begin, o->blank, o->first_lang, o->n_langs, o->suppress_blank,
                                           o->without_timestamps, o->max_initial_timestamp_index, 1, 1,
-                                          1, lp_bits, 1, 0, SP.budget ? 1 : 0, -1, hr.penalty_bits(), hr.ngram};
+                                          1, lp_bits, 1, 0, SP.budget ? 1 : 0, -1, hr.penalty_bits(), hr.ngram,
+                                          c->conf ? 1 : 0};
         ge = decode_graph(c, key, one_step, CH);
     }
     std::vector<int> row_clip(R, -1), pack, toks((size_t)R * max_tok);
+    const int ctx = d.n_text_ctx;
+    std::vector<float> cum(c->conf ? (size_t)R * ctx : 0), lang(c->conf ? (size_t)R * o->n_langs : 0);
     int next = 0, active = 0, steps = 0;
     while (true) {
         std::vector<int> free_rows;
@@ -1666,6 +1771,10 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
         for (int i = 0; i < R; ++i) fin |= row_clip[i] >= 0 && st[i].done;
         if (!fin) continue;
         HIPCHK(hipMemcpyAsync(toks.data(), c->tokens, toks.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        if (c->conf) {
+            HIPCHK(hipMemcpyAsync(cum.data(), c->lp_hist, cum.size() * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(lang.data(), c->lang_probs, lang.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        }
         HIPCHK(hipStreamSynchronize(c->stream));
         for (int i = 0; i < R; ++i) {
             const int clip = row_clip[i];
@@ -1677,11 +1786,16 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
             r->sum_logprob[clip] = q.sum_lp;
             r->no_speech_prob[clip] = q.nsp;
             r->language[clip] = q.lang;
+            if (c->conf)
+                conf_store(c, clip, &cum[(size_t)i * ctx], q.n_lp, q.n_sampled, n, &lang[(size_t)i * o->n_langs],
+                           o->n_langs);
             row_clip[i] = -1;
             --active;
         }
     }
     c->pf.decode_steps = steps;
+    if (c->conf) c->conf_res.resize(n_clips);
+    c->conf_valid = c->conf;
 }
 
 // ------------------------------ mel ----------------------------------------
@@ -2055,6 +2169,8 @@ void session_begin(osw_ctx* c, const osw_decode_opts* o) {
     SP.seed = c->seed_d;
     SP.budget = c->budget;
     SP.pos_row = 1;
+    c->conf_valid = false;
+    conf_params(c, SP, S->beam);  // (osw_set_confidences is refused while the session is open)
     S->o.suppress_tokens = nullptr;  // (copied into the mask)
     S->o.prefix_tokens = nullptr;
     S->o.language_tokens = nullptr;
@@ -2228,6 +2344,8 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
     }();
     const int beam = S->beam;
     int done = 0;
+    c->conf_res.clear();
+    c->conf_valid = c->conf;
     if (max_chunks == 0) {  // admission only: the queued windows' encoder, waited for
         session_admit(c, refill_min);
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -2261,7 +2379,8 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
                                               S->o.timestamp_begin, S->o.blank, S->o.first_lang, S->o.n_langs,
                                               S->o.suppress_blank, S->o.without_timestamps,
                                               S->o.max_initial_timestamp_index, beam, SP.num_hyp, SP.max_cand, lp_bits,
-                                              beam, 0, 1, -2, CH, S->hr.penalty_bits(), S->hr.ngram};
+                                              beam, 0, 1, -2, CH, S->hr.penalty_bits(), S->hr.ngram,
+                                              c->conf ? 1 : 0};
             hipGraphExec_t ge = decode_graph(c, key, one_step, CH);
             trace_graph(c, "launch");
             HIPCHK(hipGraphLaunch(ge, c->stream));
@@ -2285,6 +2404,15 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
         std::vector<int> toks((size_t)hi * S->max_tok);
         HIPCHK(hipMemcpyAsync(toks.data(), beam > 1 ? c->btok : c->tokens, toks.size() * 4, hipMemcpyDeviceToHost,
                               c->stream));
+        const int n_langs = S->o.n_langs;
+        std::vector<float> cum, lang;
+        if (c->conf) {  // beam: the best hypothesis' history per window slot; greedy: the rows' own
+            cum.resize((size_t)hi * S->ctx);
+            lang.resize((size_t)hi * n_langs);
+            HIPCHK(hipMemcpyAsync(cum.data(), beam > 1 ? c->best_lp : c->lp_hist, cum.size() * 4, hipMemcpyDeviceToHost,
+                                  c->stream));
+            HIPCHK(hipMemcpyAsync(lang.data(), c->lang_probs, lang.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        }
         HIPCHK(hipStreamSynchronize(c->stream));
         for (int slot : fin) {
             const SelState& q = st[(size_t)slot * beam];
@@ -2295,6 +2423,9 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
             r->sum_logprob[done] = beam > 1 ? bw[slot].best_raw : q.sum_lp;
             r->no_speech_prob[done] = q.nsp;
             r->language[done] = q.lang;
+            if (c->conf)
+                conf_store(c, done, &cum[(size_t)slot * S->ctx], beam > 1 ? bw[slot].best_nlp : q.n_lp, n0, n,
+                           &lang[(size_t)slot * n_langs], n_langs);
             tags[done] = S->slot_tag[slot];
             S->slot_tag[slot] = -1;
             --S->active;
@@ -2309,7 +2440,7 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
 // ============================== C ABI =======================================
 extern "C" {
 
-const char* osw_version(void) { return "osw-hip 0.1 gfx950"; }
+const char* osw_version(void) { return "osw-hip 0.2 gfx950"; }
 const char* osw_last_error(void) { return g_err.c_str(); }
 
 int osw_device_count(int32_t* out) {
@@ -2590,6 +2721,60 @@ int osw_decode_windows(osw_ctx* c, int32_t n, const osw_decode_opts* opts, osw_w
         DeviceScope dev_scope_((c->device));
         LaneCall call_(c);
         decode(c, n, opts, res);
+        resolve_events(c);
+    });
+}
+
+int osw_set_confidences(osw_ctx* c, int32_t enable) {
+    return guard([&] {
+        REQUIRE(c, "null ctx");
+        std::lock_guard<std::mutex> lk(c->mu);
+        REQUIRE(!c->sess, "a decode session is open on this context (osw_session_end first)");
+        c->conf = enable != 0;
+        c->conf_valid = false;
+        c->conf_res.clear();
+    });
+}
+
+namespace {
+const osw_ctx::ConfResult* conf_result(osw_ctx* c, int32_t i) {
+    if (!c->conf || !c->conf_valid)
+        throw OswError(OSW_ESTATE, "no confidences recorded (osw_set_confidences(ctx, 1), then a decode call)");
+    REQUIRE(i >= 0 && (size_t)i < c->conf_res.size(), "result index out of range");
+    return &c->conf_res[i];
+}
+}  // namespace
+
+int osw_get_token_logprobs(osw_ctx* c, int32_t i, float* cum, int32_t cap, int32_t* n) {
+    return guard([&] {
+        REQUIRE(c && n, "null argument");
+        std::lock_guard<std::mutex> lk(c->mu);
+        const osw_ctx::ConfResult& q = *conf_result(c, i);
+        *n = (int32_t)q.cum.size();
+        if (!cum) return;  // (query the count)
+        REQUIRE(cap >= *n, "output buffer too small");
+        std::copy(q.cum.begin(), q.cum.end(), cum);
+    });
+}
+
+int osw_get_language_probs(osw_ctx* c, int32_t i, float* probs, int32_t n_langs) {
+    return guard([&] {
+        REQUIRE(c && probs, "null argument");
+        std::lock_guard<std::mutex> lk(c->mu);
+        const osw_ctx::ConfResult& q = *conf_result(c, i);
+        REQUIRE(n_langs == (int32_t)q.lang.size(), "n_langs differs from the decode call's");
+        std::copy(q.lang.begin(), q.lang.end(), probs);
+    });
+}
+
+int osw_detect_language(osw_ctx* c, int32_t n, const osw_decode_opts* opts, float* probs, float* raw_logits) {
+    return guard([&] {
+        REQUIRE(c, "null ctx");
+        std::lock_guard<std::mutex> lk(c->mu);
+        REQUIRE(!c->sess, "a decode session is open on this context (osw_session_end first)");
+        DeviceScope dev_scope_((c->device));
+        LaneCall call_(c);
+        detect_language(c, n, opts, probs, raw_logits);
         resolve_events(c);
     });
 }

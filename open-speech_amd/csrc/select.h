@@ -224,6 +224,19 @@ __device__ __forceinline__ SelPart combine_parts(const SelPart* __restrict__ par
     return r;
 }
 
+// Confidences: softmax over the n_langs raw language logits [first_lang, first_lang + n_langs)
+// (CTranslate2 detect_language's distribution: over the language tokens only), by one thread
+// in index order, so a window's values depend on nothing but its own logits.
+template <class LG>
+__device__ __forceinline__ void lang_softmax(LG lg, const SelParams& P, float* __restrict__ out) {
+    float m = -INFINITY;
+    for (int i = 0; i < P.n_langs; ++i) m = fmaxf(m, lg(P.first_lang + i));
+    float sum = 0.f;
+    for (int i = 0; i < P.n_langs; ++i) sum += __expf(lg(P.first_lang + i) - m);
+    const float inv = 1.f / sum;
+    for (int i = 0; i < P.n_langs; ++i) out[i] = __expf(lg(P.first_lang + i) - m) * inv;
+}
+
 // grid B, 64 threads: combine the slices in fixed order, apply the timestamp-mass
 // rule, pick the token, update the window state.
 // getr() returns the row's combined slice statistics (called only in the modes that use them).
@@ -255,6 +268,10 @@ __device__ __forceinline__ void select_finalize(const float* __restrict__ logits
     const float lse_all = r.m_all + __logf(r.s_all);
     if (mode == SEL_SOT) {
         s.nsp = __expf(lg(P.no_speech) - lse_all);
+        // confidences: the window's language distribution from the same raw logits, whether the
+        // language is detected or given; the first of the window's lp_group rows writes it
+        if (P.lang_probs && b % P.lp_group == 0)
+            lang_softmax(lg, P, P.lang_probs + (int64_t)(b / P.lp_group) * P.n_langs);
         int next = prompt[b * P.pstride + step + 1];
         if (next < 0) {
             next = r.i_text;  // language detection: argmax over language tokens
@@ -293,6 +310,10 @@ __device__ __forceinline__ void select_finalize(const float* __restrict__ logits
         lp = lg(P.eot) - lse_all;
     }
     s.sum_lp += lp;
+    if (P.lp_hist && n < P.lp_stride) {  // confidences: the cumulative value itself, one plain store
+        P.lp_hist[(int64_t)b * P.lp_stride + n] = s.sum_lp;
+        s.n_lp = n + 1;
+    }
     if (next == P.eot) {
         s.done = 1;
     } else {

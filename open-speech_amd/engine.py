@@ -41,6 +41,10 @@ class DecodeConfig:
     # over what the row sampled so far in its window: 1.0 / 0 = off
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
+    # per-token log-probabilities and language probabilities (osw_set_confidences): what
+    # CTranslate2's return_scores and faster-whisper's language_probability / all_language_probs
+    # give; tokens, sum_logprob, no_speech_prob and language are the same bits on and off
+    confidences: bool = False
 
 
 @dataclass
@@ -50,6 +54,23 @@ class WindowOutput:
     no_speech_prob: float
     language: int
     logits: np.ndarray | None = field(default=None, repr=False)
+    # DecodeConfig.confidences (None when off).  cum_logprobs: the device's fp32 cumulative
+    # log-probability after each token, with a closing <|endoftext|> entry when the row ended with
+    # one (its last entry is sum_logprob, bit for bit); token_logprobs: their float64 differences,
+    # one per returned token; eot_logprob: the closing step's, None for a row cut at max_length;
+    # language_probs: softmax over the language tokens at <|startoftranscript|> [n_langs]
+    token_logprobs: list | None = None
+    eot_logprob: float | None = None
+    language_probs: np.ndarray | None = field(default=None, repr=False)
+    cum_logprobs: np.ndarray | None = field(default=None, repr=False)
+
+
+def split_cumulative(cum: np.ndarray, n_tokens: int):
+    """(token_logprobs, eot_logprob) from a window's cumulative fp32 log-probabilities: the
+    differences of neighbours in float64; entry ``n_tokens``, if present, is the <|endoftext|>
+    step's."""
+    lp = np.diff(np.asarray(cum, dtype=np.float64), prepend=0.0)
+    return lp[:n_tokens].tolist(), (float(lp[n_tokens]) if len(lp) > n_tokens else None)
 
 
 @dataclass
@@ -93,6 +114,7 @@ class WhisperEngine:
             _lib.check(self.lib.osw_create_sibling(_parent.ctx, max_batch, C.byref(ctx)), "osw_create_sibling")
         self.ctx = ctx
         self._nframes: list[int] = []
+        self._conf = False
 
     def sibling(self, max_batch: int | None = None) -> "WhisperEngine":
         """A second engine on the same GPU sharing this one's (loaded) weights, with its
@@ -242,19 +264,58 @@ class WhisperEngine:
             dump_steps=dump_steps)
         return r, bufs, dump
 
-    @staticmethod
-    def _outputs(n, bufs, dump) -> list[WindowOutput]:
-        return [WindowOutput(tokens=bufs["tokens"][i, :bufs["n"][i]].tolist(), sum_logprob=float(bufs["lp"][i]),
+    def _set_confidences(self, on: bool) -> None:
+        if bool(on) != self._conf:
+            _lib.check(self.lib.osw_set_confidences(self.ctx, int(bool(on))), "osw_set_confidences")
+            self._conf = bool(on)
+
+    def _outputs(self, n, bufs, dump, conf: bool = False) -> list[WindowOutput]:
+        outs = [WindowOutput(tokens=bufs["tokens"][i, :bufs["n"][i]].tolist(), sum_logprob=float(bufs["lp"][i]),
                              no_speech_prob=float(bufs["nsp"][i]), language=int(bufs["lang"][i]),
                              logits=None if dump is None else dump[i]) for i in range(n)]
+        if conf:
+            self._fetch_confidences(outs)
+        return outs
+
+    def _fetch_confidences(self, outs: list) -> None:
+        """The confidences of the windows the last decode call returned, fetched after it
+        (osw_get_alignment_matrix's way): host copies, no device work."""
+        f32p = C.POINTER(C.c_float)
+        for i, out in enumerate(outs):
+            cum = np.zeros(self.dims.n_text_ctx + 1, np.float32)
+            cnt = C.c_int32()
+            _lib.check(self.lib.osw_get_token_logprobs(self.ctx, i, cum.ctypes.data_as(f32p), len(cum),
+                                                       C.byref(cnt)), "osw_get_token_logprobs")
+            probs = np.zeros(self.st.n_langs, np.float32)
+            _lib.check(self.lib.osw_get_language_probs(self.ctx, i, probs.ctypes.data_as(f32p), len(probs)),
+                       "osw_get_language_probs")
+            out.cum_logprobs = cum[:cnt.value].copy()
+            out.token_logprobs, out.eot_logprob = split_cumulative(out.cum_logprobs, len(out.tokens))
+            out.language_probs = probs
+
+    def detect_language(self, n: int, return_logits: bool = False):
+        """Language probabilities [n][n_langs] of the ``n`` windows last encoded
+        (osw_detect_language: one decoder step on <|startoftranscript|>; replaces
+        ``WhisperModel.detect_language``).  A later ``decode`` of the same windows is not
+        affected.  ``return_logits``: also the raw logits the softmax was taken over."""
+        o, keep = self._opts(DecodeConfig(), n, None)
+        f32p = C.POINTER(C.c_float)
+        probs = np.zeros((n, self.st.n_langs), np.float32)
+        raw = np.zeros((n, self.st.n_langs), np.float32) if return_logits else None
+        _lib.check(self.lib.osw_detect_language(self.ctx, int(n), C.byref(o), probs.ctypes.data_as(f32p),
+                                                raw.ctypes.data_as(f32p) if raw is not None else None),
+                   "osw_detect_language")
+        del keep
+        return (probs, raw) if return_logits else probs
 
     def decode(self, n: int, cfg: DecodeConfig, prefix: list | None = None, dump_steps: int = 0,
                languages: list | None = None) -> list[WindowOutput]:
         o, keep = self._opts(cfg, n, prefix, languages)
         r, bufs, dump = self._result(n, dump_steps)
+        self._set_confidences(cfg.confidences)
         _lib.check(self.lib.osw_decode_windows(self.ctx, n, C.byref(o), C.byref(r)), "osw_decode_windows")
         del keep
-        return self._outputs(n, bufs, dump)
+        return self._outputs(n, bufs, dump, cfg.confidences)
 
     def transcribe_batch(self, clips: list, cfg: DecodeConfig, device_pcm: int | None = None,
                          offsets: np.ndarray | None = None) -> list[WindowOutput]:
@@ -270,10 +331,11 @@ class WhisperEngine:
         n = len(offs) - 1
         o, keep = self._opts(cfg, n, None)
         r, bufs, dump = self._result(n, 0)
+        self._set_confidences(cfg.confidences)
         _lib.check(self.lib.osw_transcribe_batch(self.ctx, ptr, offs.ctypes.data_as(C.POINTER(C.c_int64)), n, on_dev,
                                                  C.byref(o), C.byref(r)), "osw_transcribe_batch")
         del keep
-        return self._outputs(n, bufs, dump)
+        return self._outputs(n, bufs, dump, cfg.confidences)
 
     def transcribe_refill(self, clips: list, cfg: DecodeConfig, device_pcm: int | None = None,
                           offsets: np.ndarray | None = None, refill_min: int | None = None) -> list[WindowOutput]:
@@ -297,10 +359,11 @@ class WhisperEngine:
         n = len(offs) - 1
         o, keep = self._opts(cfg, n, None)
         r, bufs, dump = self._result(n, 0)
+        self._set_confidences(cfg.confidences)
         _lib.check(self.lib.osw_transcribe_refill(self.ctx, ptr, offs.ctypes.data_as(C.POINTER(C.c_int64)), n, on_dev,
                                                   C.byref(o), C.byref(r), int(refill_min)), "osw_transcribe_refill")
         del keep
-        return self._outputs(n, bufs, dump)
+        return self._outputs(n, bufs, dump, cfg.confidences)
 
     # ------------------------------------------------------------ decode sessions
     def session_begin(self, cfg: DecodeConfig) -> None:
@@ -310,6 +373,8 @@ class WhisperEngine:
         only (greedy or beam search, beam_size <= 5); ``cfg.token_budget`` is per window
         (``session_add``), not here."""
         o, keep = self._opts(dataclasses.replace(cfg, token_budget=None), 0, None)
+        self._set_confidences(cfg.confidences)  # (the session keeps the setting it begins with)
+        self._sess_conf = bool(cfg.confidences)
         _lib.check(self.lib.osw_session_begin(self.ctx, C.byref(o)), "osw_session_begin")
         del keep
         self._sess_res = self._result(self.max_batch, 0)
@@ -343,14 +408,14 @@ class WhisperEngine:
                    "osw_session_add")
 
     def session_step(self, max_chunks: int = 64, refill_min: int = 1):
-        """Run decoder chunks until windows finish (at most ``max_chunks`` chunks of 8
+        """Run decoder chunks until windows finish (at most ``max_chunks`` chunks of 4
         steps).  Returns ([(tag, WindowOutput)], n_active, n_queued)."""
         r, bufs, _ = self._sess_res
         nd, na, nq = C.c_int32(), C.c_int32(), C.c_int32()
         _lib.check(self.lib.osw_session_step(self.ctx, int(max_chunks), int(refill_min), C.byref(r),
                                              self._sess_tags.ctypes.data_as(C.POINTER(C.c_int64)), self.max_batch,
                                              C.byref(nd), C.byref(na), C.byref(nq)), "osw_session_step")
-        outs = self._outputs(nd.value, bufs, None)
+        outs = self._outputs(nd.value, bufs, None, getattr(self, "_sess_conf", False))
         return [(int(self._sess_tags[i]), outs[i]) for i in range(nd.value)], na.value, nq.value
 
     def session_release_clip(self, clip: int) -> None:

@@ -74,6 +74,12 @@ class TranscribeOptions:
     # penalty > 0, size >= 0); 1.0 / 0 = off
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
+    # per-token log-probabilities on every segment and the detected language's probability
+    # (OpenAI include[]=logprobs; faster-whisper language_probability / all_language_probs)
+    token_logprobs: bool = False
+    # language detection only (faster-whisper WhisperModel.detect_language, one window): the
+    # result carries the language and its probabilities, no segments
+    detect_only: bool = False
 
     def __post_init__(self):
         if not float(self.repetition_penalty) > 0:
@@ -86,7 +92,8 @@ class TranscribeOptions:
                 self.without_timestamps, tuple(self.suppress_tokens), self.suppress_blank, self.beam_size,
                 self.patience, self.length_penalty, self.temperature, self.best_of, self.tokens_per_second,
                 self.max_new_tokens, self.word_timestamps, self.prepend_punctuations, self.append_punctuations,
-                float(self.repetition_penalty), int(self.no_repeat_ngram_size))
+                float(self.repetition_penalty), int(self.no_repeat_ngram_size), bool(self.token_logprobs),
+                bool(self.detect_only))
 
 
 @dataclass
@@ -110,6 +117,7 @@ class Segment:
     compression_ratio: float
     no_speech_prob: float
     words: list | None = None      # [Word] with word_timestamps, else None
+    token_logprobs: list | None = None   # with TranscribeOptions.token_logprobs: one per entry of ``tokens``
 
 
 @dataclass
@@ -117,11 +125,21 @@ class ClipResult:
     segments: list = field(default_factory=list)
     language: str = "en"
     duration: float = 0.0
+    # faster-whisper TranscriptionInfo semantics: a detected language's probability and every
+    # language's (code, probability) by falling probability, from the window that set the clip's
+    # language (needs TranscribeOptions.token_logprobs or detect_only); a language given by the
+    # caller: 1.0 and None
+    language_probability: float | None = None
+    all_language_probs: list | None = None
 
 
 def split_segments_by_timestamps(tokens: list, tb: int, time_offset: float, segment_size: int,
-                                 segment_duration: float, seek: int):
-    """faster-whisper ``_split_segments_by_timestamps`` (openai transcribe.py logic)."""
+                                 segment_duration: float, seek: int, token_logprobs: list | None = None):
+    """faster-whisper ``_split_segments_by_timestamps`` (openai transcribe.py logic).  With
+    ``token_logprobs`` (one per token) every segment also carries the slice of them that
+    matches its ``tokens``."""
+    if token_logprobs is not None and len(token_logprobs) != len(tokens):
+        raise ValueError("one log-probability per token")
     current = []
     single_timestamp_ending = len(tokens) >= 2 and tokens[-2] < tb <= tokens[-1]
     consecutive = [i for i in range(len(tokens)) if i > 0 and tokens[i] >= tb and tokens[i - 1] >= tb]
@@ -136,6 +154,8 @@ def split_segments_by_timestamps(tokens: list, tb: int, time_offset: float, segm
             end_pos = sliced[-1] - tb
             current.append(dict(seek=seek, start=time_offset + start_pos * TIME_PRECISION,
                                 end=time_offset + end_pos * TIME_PRECISION, tokens=sliced))
+            if token_logprobs is not None:
+                current[-1]["token_logprobs"] = token_logprobs[last_slice:cur]
             last_slice = cur
         if single_timestamp_ending:
             seek += segment_size
@@ -148,6 +168,8 @@ def split_segments_by_timestamps(tokens: list, tb: int, time_offset: float, segm
         if ts and ts[-1] != tb:
             duration = (ts[-1] - tb) * TIME_PRECISION
         current.append(dict(seek=seek, start=time_offset, end=time_offset + duration, tokens=tokens))
+        if token_logprobs is not None:
+            current[-1]["token_logprobs"] = token_logprobs
         seek += segment_size
     return current, seek, single_timestamp_ending
 
@@ -170,6 +192,8 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
     """Run the seek loop for a batch of int16 clips on one engine (all share `opts`)."""
     st = tok.special
     nf = engine.log_mel(pcm_list)
+    if opts.detect_only:
+        return _detect_clips(engine, pcm_list, nf, tok)
     lang_token = tok.language_token(opts.language) if (opts.language and opts.task == "transcribe") else None
     init_tokens = tok.encode(" " + opts.initial_prompt.strip()) if opts.initial_prompt else []
     states = []
@@ -177,6 +201,8 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
         s = _ClipState(idx=i, content_frames=max(0, n - 1), all_tokens=list(init_tokens), lang_token=lang_token)
         s.result.duration = len(pcm_list[i]) / 16000.0
         s.done = s.content_frames <= 0
+        if lang_token is not None:
+            s.result.language_probability = 1.0
         states.append(s)
     max_init = int(round(opts.max_initial_timestamp / TIME_PRECISION))
     sampling = opts.temperature > 0
@@ -216,7 +242,8 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
                                    length_penalty=opts.length_penalty, temperature=opts.temperature,
                                    best_of=opts.best_of, seed=(opts.seed + 0x9E3779B1 * calls) & (2**64 - 1),
                                    repetition_penalty=float(opts.repetition_penalty),
-                                   no_repeat_ngram_size=int(opts.no_repeat_ngram_size))
+                                   no_repeat_ngram_size=int(opts.no_repeat_ngram_size),
+                                   confidences=bool(opts.token_logprobs))
                 if opts.tokens_per_second:
                     cfg.token_budget = tuple(int(np.ceil(opts.tokens_per_second * z * FRAME_SEC)) + 2
                                              for _, _, z in wins)
@@ -248,6 +275,34 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
     return [s.result for s in states]
 
 
+def _set_language_probs(res: ClipResult, probs, lang_token: int, tok: WhisperTokenizer) -> None:
+    """faster-whisper's language_probability / all_language_probs from the window that set the
+    clip's language (nothing when the engine recorded no probabilities)."""
+    if probs is None:
+        return
+    p = np.asarray(probs, dtype=np.float64)
+    res.language_probability = float(p[lang_token - tok.special.first_lang])
+    res.all_language_probs = [(tok.language_code(tok.special.first_lang + int(i)), float(p[i]))
+                              for i in np.argsort(-p, kind="stable")]
+
+
+def _detect_clips(engine, pcm_list: list, nf: list, tok: WhisperTokenizer) -> list[ClipResult]:
+    """TranscribeOptions.detect_only: the language of every clip's first 30 s window
+    (faster-whisper ``detect_language`` with language_detection_segments = 1)."""
+    out = []
+    B = max(1, engine.max_batch)
+    for lo in range(0, len(pcm_list), B):
+        idx = list(range(lo, min(lo + B, len(pcm_list))))
+        engine.encode([(i, 0, max(1, min(N_FRAMES, nf[i] - 1))) for i in idx])
+        probs = engine.detect_language(len(idx))
+        for i, p in zip(idx, probs):
+            lang = tok.special.first_lang + int(np.argmax(p))
+            res = ClipResult(language=tok.language_code(lang), duration=len(pcm_list[i]) / 16000.0)
+            _set_language_probs(res, p, lang, tok)
+            out.append(res)
+    return out
+
+
 # ------------------------------------------------------------ one clip at a time
 # (the runner's decode-session lanes, runner.py: each clip's seek loop advances on its own,
 # its next window queued into the session as soon as the previous one is consumed)
@@ -257,6 +312,8 @@ def session_supported(opts: TranscribeOptions) -> bool:
     temperature 0, beam_size <= 5, and no max_new_tokens (whose max_length depends on
     each window's prompt length)."""
     if opts.word_timestamps:   # the alignment pass needs the window's cross-K/V of a batched decode call
+        return False
+    if opts.detect_only:       # one decoder step per clip, no seek loop
         return False
     return not (opts.temperature > 0) and opts.max_new_tokens is None and 1 <= int(opts.beam_size) <= 5
 
@@ -269,7 +326,7 @@ def session_config(opts: TranscribeOptions, suppress: tuple) -> DecodeConfig:
                         max_initial_timestamp_index=int(round(opts.max_initial_timestamp / TIME_PRECISION)),
                         beam_size=max(1, int(opts.beam_size)), patience=opts.patience,
                         length_penalty=opts.length_penalty, repetition_penalty=float(opts.repetition_penalty),
-                        no_repeat_ngram_size=int(opts.no_repeat_ngram_size))
+                        no_repeat_ngram_size=int(opts.no_repeat_ngram_size), confidences=bool(opts.token_logprobs))
 
 
 def clip_state(idx: int, pcm: np.ndarray, opts: TranscribeOptions, tok: WhisperTokenizer) -> _ClipState:
@@ -281,6 +338,8 @@ def clip_state(idx: int, pcm: np.ndarray, opts: TranscribeOptions, tok: WhisperT
                    lang_token=lang_token)
     s.result.duration = len(pcm) / 16000.0
     s.done = s.content_frames <= 0
+    if lang_token is not None:
+        s.result.language_probability = 1.0
     return s
 
 
@@ -315,6 +374,7 @@ def _plan(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperTokenize
     _, seek, segment_size = win
     if s.lang_token is None:
         s.lang_token = out.language
+        _set_language_probs(s.result, getattr(out, "language_probs", None), out.language, tok)
     tokens = out.tokens
     avg_logprob = out.sum_logprob / (len(tokens) + 1)
     text = tok.decode(tokens).strip()
@@ -328,8 +388,9 @@ def _plan(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperTokenize
             s.done = s.seek >= s.content_frames
             return None
     time_offset = seek * FRAME_SEC
+    lps = getattr(out, "token_logprobs", None) if opts.token_logprobs else None
     segs, new_seek, single_ending = split_segments_by_timestamps(tokens, st.timestamp_begin, time_offset, segment_size,
-                                                                 segment_size * FRAME_SEC, seek)
+                                                                 segment_size * FRAME_SEC, seek, lps)
     text_tokens = [int(t) for sg in segs for t in sg["tokens"] if t < st.eot]
     return dict(segs=segs, new_seek=new_seek, single_ending=single_ending, avg_logprob=avg_logprob, cr=cr,
                 text_tokens=text_tokens, time_offset=time_offset)
@@ -358,7 +419,9 @@ def _apply(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperTokeniz
                                          text=txt, tokens=list(t), temperature=opts.temperature,
                                          avg_logprob=avg_logprob, compression_ratio=cr,
                                          no_speech_prob=out.no_speech_prob,
-                                         words=[Word(**w) for w in sg["words"]] if "words" in sg else None))
+                                         words=[Word(**w) for w in sg["words"]] if "words" in sg else None,
+                                         token_logprobs=list(sg["token_logprobs"]) if "token_logprobs" in sg
+                                         else None))
     if not opts.condition_on_previous_text or opts.temperature > opts.prompt_reset_on_temperature:
         s.prompt_reset_since = len(s.all_tokens)
     s.seek = new_seek
@@ -537,9 +600,34 @@ def to_vtt(segments) -> str:
     return "\n".join(lines)
 
 
-def shape_response(task: str, res: ClipResult, response_format: str) -> dict:
-    """Return shapes by format (src/backends/faster_whisper.py:251-281)."""
+def logprobs_list(res: ClipResult, tok: WhisperTokenizer) -> list:
+    """OpenAI's ``include[]=logprobs`` shape over the text tokens (ids below <|endoftext|>) of
+    every segment, in order."""
+    eot = tok.special.eot
+    out = []
+    for sg in res.segments:
+        for t, lp in zip(sg.tokens, sg.token_logprobs or ()):
+            if t < eot:
+                b = tok.token_bytes(t)
+                out.append({"token": b.decode("utf-8", errors="replace"), "logprob": float(lp), "bytes": list(b)})
+    return out
+
+
+def shape_response(task: str, res: ClipResult, response_format: str, tok: WhisperTokenizer | None = None,
+                   logprobs: bool = False) -> dict:
+    """Return shapes by format (src/backends/faster_whisper.py:251-281).  ``logprobs`` (with
+    ``tok``): ``json`` / ``verbose_json`` gain ``logprobs`` and ``language_probability``,
+    ``verbose_json`` segments ``token_logprobs``; the other formats and ``logprobs=False`` are
+    the reference's shapes unchanged."""
     full = "".join(sg.text for sg in res.segments).strip()
+    if logprobs and response_format in ("json", "verbose_json"):
+        out = verbose_dict(task, res) if response_format == "verbose_json" else {"text": full}
+        if response_format == "verbose_json":
+            for d, sg in zip(out["segments"], res.segments):
+                d["token_logprobs"] = [float(x) for x in (sg.token_logprobs or [])]
+        out["logprobs"] = logprobs_list(res, tok)
+        out["language_probability"] = res.language_probability
+        return out
     if response_format == "verbose_json":
         return verbose_dict(task, res)
     if response_format == "text":

@@ -33,6 +33,25 @@ _MISC = set("♩♪♫♬♭♮♯")
 UNSPACED_LANGUAGES = frozenset({"zh", "ja", "th", "lo", "my", "yue"})
 
 
+_BYTE_DECODER: dict = {}
+
+
+def _byte_decoder() -> dict:
+    """Byte-level BPE's printable stand-in character -> byte (the GPT-2 ``bytes_to_unicode``
+    table inverted): printable Latin-1 bytes stand for themselves, the other 68 take the code
+    points from 256 up in byte order."""
+    if not _BYTE_DECODER:
+        keep = list(range(ord("!"), ord("~") + 1)) + list(range(0xA1, 0xAD)) + list(range(0xAE, 0x100))
+        n = 0
+        for b in range(256):
+            if b in keep:
+                _BYTE_DECODER[chr(b)] = b
+            else:
+                _BYTE_DECODER[chr(256 + n)] = b
+                n += 1
+    return _BYTE_DECODER
+
+
 class WhisperTokenizer:
     """Thin wrapper; text decoding needs a ``tokenizer.json`` (``tokenizers`` package)."""
 
@@ -59,6 +78,21 @@ class WhisperTokenizer:
         if self._tok is None:
             return "".join(f"<|{t}|>" for t in text_tokens)
         return self._tok.decode(text_tokens, skip_special_tokens=False)
+
+    def token_bytes(self, token: int) -> bytes:
+        """The UTF-8 bytes one token stands for (a token may hold part of a character, so the
+        bytes of consecutive tokens concatenate to the text's; OpenAI's logprobs ``bytes``).
+        Without a ``tokenizer.json``: the bytes of ``decode``'s ``<|id|>`` stand-in."""
+        t = int(token)
+        if self._tok is None:
+            return f"<|{t}|>".encode()
+        piece = self._tok.id_to_token(t)
+        if piece is None:
+            return b""
+        table = _byte_decoder()
+        if all(ch in table for ch in piece):      # byte-level BPE piece
+            return bytes(table[ch] for ch in piece)
+        return piece.encode("utf-8")              # an added (special) token: its literal text
 
     def _decode_with_specials(self, tokens) -> str:
         """Text tokens decoded; <|endoftext|> kept as its own marker (it closes the word
