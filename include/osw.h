@@ -36,6 +36,8 @@
  *                 transcribe without it (src/backends/faster_whisper.py:235-246)
  *   osw_get_alignment_matrix / osw_debug_dtw
  *       stage-level read-back and the DTW kernel alone, used only by the parity tests
+ *   osw_debug_enc_attn / osw_debug_dec_xattn / osw_debug_dec_self_attn
+ *       one attention launch on host data, used only by the parity tests
  *   osw_decode_opts::repetition_penalty / no_repeat_ngram_size (+ osw_debug_history_rules)
  *       replace   WhisperModel.transcribe(..., repetition_penalty=, no_repeat_ngram_size=):
  *                 ctranslate2's RepetitionPenalty / NoRepeatNgram logits processors [upstream],
@@ -185,6 +187,10 @@ const char* osw_version(void);
 const char* osw_last_error(void);
 int osw_device_count(int32_t* out);
 
+/* Model widths served: n_audio_state == n_text_state in {128, 256, 384, 512, 768, 1024, 1280}
+ * with 64-wide heads (512 / 768 / 1024 / 1280 are Whisper base / small / medium / large).  Any
+ * other width, the multiples of 128 in between (640, 896, 1152) included, has no LayerNorm
+ * kernel and returns OSW_EINVAL. */
 int osw_create(const osw_dims* dims, int32_t device, int32_t max_batch, osw_ctx** out);
 int osw_destroy(osw_ctx* ctx);
 /* A second context on the parent's device that SHARES the parent's (finalized)
@@ -393,6 +399,43 @@ int osw_encoder_layer_debug(osw_ctx* ctx, int32_t layer, const float* x, float* 
  * runs `iters` times and stores the mean kernel time (ms, HIP events) in *ms. */
 int osw_debug_gemm(osw_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t variant, const void* A, const void* W,
                    float* C, int32_t iters, float* ms);
+
+/* ---- one attention launch on host data (parity tests: tests/test_gpu_attention.py) ----
+ * Each call copies its inputs to temporary device buffers, launches the kernel once on the
+ * context's stream and copies the result back; like osw_debug_gemm they allocate, so they wait
+ * for a capture in progress.  They replace no reference interface: the reference's attention
+ * runs inside CTranslate2 [upstream].
+ *
+ * Encoder self-attention softmax(Q Kᵀ / 8) V over the T = 1500 positions: qkv fp16
+ * [3][nb][H][1500][64] (the QKV GEMM's head-major output), out fp16 [nb * 1500][H * 64].  nb <= 64
+ * and H <= 20 are independent of the context's dims.  form 0: the production launcher's choice
+ * (64-query workgroups below 512 units of 128, lazy running max, unpipelined, unless the OSW_ATTN_*
+ * environment says otherwise); an explicit form is OSW_ATTN_FORM | any of _EAGER (rescale O on
+ * every key tile), _QB128 (128 queries per workgroup instead of 64), _PIPE (software-pipelined). */
+#define OSW_ATTN_FORM 1
+#define OSW_ATTN_FORM_EAGER 2
+#define OSW_ATTN_FORM_QB128 4
+#define OSW_ATTN_FORM_PIPE 8
+int osw_debug_enc_attn(osw_ctx* ctx, const void* qkv, int32_t nb, int32_t H, int32_t form, void* out);
+/* Decoder cross-attention of `rows` = windows x beam decoder rows (beam <= 8, windows <= max_batch)
+ * over each window's 1500 encoder keys, with the context's n_text_head heads H and width D = 64 H:
+ * q_slabs fp32 [ks][rows][D] are the q projection's split-K partials (q = fp16(bias + their sum)),
+ * bias [D] or NULL, K and V fp16 [windows][H][1500][64]; out fp32 [rows][D] = the kernel's fp16
+ * hi + lo output pair, summed.  legacy != 0 passes no workspace, which selects the one-workgroup-
+ * per-(row, head) kernel; otherwise the key-chunk kernels run: beam 1 and ks > 8 the VALU form,
+ * beam > 1 with ks <= 8 the MFMA form.  The context's arrival tickets it used are zero on return. */
+int osw_debug_dec_xattn(osw_ctx* ctx, const float* q_slabs, int32_t ks, const float* bias, const void* K,
+                        const void* V, int32_t rows, int32_t beam, int32_t legacy, float* out);
+/* Decoder self-attention step of `rows` rows with the context's H, D and ctx = n_text_ctx:
+ * qkv_slabs fp32 [ks][rows][3 D] are the qkv projection's split-K partials, bias [3 D]; kcache and
+ * vcache fp16 [rows][H][ctx][64] are read, get fp16(k) and fp16(v) of row r written at position
+ * pos[r] (pos_per_row != 0) or pos[0], and are copied back; the row attends positions 0 .. pos.
+ * ancestry [rows][ctx] (beam search; NULL: every key is the row's own): key p < pos of row r is read
+ * from row ancestry[r][p]'s cache, rows = windows x group.  out fp32 [rows][D] = hi + lo.  The form
+ * is the production launcher's: <= 8 rows issue V with K, more rows V late; ancestry gathers. */
+int osw_debug_dec_self_attn(osw_ctx* ctx, const float* qkv_slabs, int32_t ks, const float* bias, void* kcache,
+                            void* vcache, int32_t rows, const int32_t* pos, int32_t pos_per_row,
+                            const int32_t* ancestry, int32_t group, float* out);
 
 /* Test hook for the concurrency contract: holds a stream capture open on the context's
  * stream for hold_ms (under the same locks as a decode-graph capture) and fails if it was

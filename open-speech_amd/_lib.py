@@ -123,6 +123,13 @@ _SIGS = {
     "osw_encoder_layer_debug": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_float), C.c_int32]),
     "osw_debug_gemm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                  P(C.c_float), C.c_int32, P(C.c_float)]),
+    # one attention launch on host data (parity tests)
+    "osw_debug_enc_attn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "osw_debug_dec_xattn": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, P(C.c_float), C.c_void_p, C.c_void_p,
+                                      C.c_int32, C.c_int32, C.c_int32, P(C.c_float)]),
+    "osw_debug_dec_self_attn": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, P(C.c_float), C.c_void_p, C.c_void_p,
+                                          C.c_int32, P(C.c_int32), C.c_int32, P(C.c_int32), C.c_int32,
+                                          P(C.c_float)]),
     "osw_debug_hold_capture": (C.c_int, [C.c_void_p, C.c_int32]),
     "osw_set_encoder_baton_min": (C.c_int, [C.c_void_p, C.c_int32]),
     "osw_set_profiling": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -309,6 +309,25 @@ __global__ __launch_bounds__(256, 2) void enc_attn_kernel(const h16* __restrict_
 }
 }  // namespace
 
+// One explicit form of the kernel: eager (rescale O on every tile) or lazy, 64- (small) or
+// 128-query workgroups, the software-pipelined step or not; grid_cap bounds the grid (a
+// capped grid loops over the units).  launch_enc_attn chooses; osw_debug_enc_attn names one.
+void launch_enc_attn_form(const h16* qkv, h16* out, int T, int H, int nb, bool eager, bool small, bool pipe,
+                          int grid_cap, hipStream_t s) {
+    const int nqb = small ? (T + 63) / 64 : (T + QB - 1) / QB;
+    const int nwg = nqb * H * nb;
+    const int grid = std::min(nwg, grid_cap);
+#define OSW_ATTN_LAUNCH(L, Q, P) enc_attn_kernel<L, Q, P><<<grid, 256, 0, s>>>(qkv, out, T, H, nb, nqb)
+    if (small) {
+        if (eager) pipe ? OSW_ATTN_LAUNCH(false, 1, true) : OSW_ATTN_LAUNCH(false, 1, false);
+        else pipe ? OSW_ATTN_LAUNCH(true, 1, true) : OSW_ATTN_LAUNCH(true, 1, false);
+    } else {
+        if (eager) pipe ? OSW_ATTN_LAUNCH(false, 2, true) : OSW_ATTN_LAUNCH(false, 2, false);
+        else pipe ? OSW_ATTN_LAUNCH(true, 2, true) : OSW_ATTN_LAUNCH(true, 2, false);
+    }
+#undef OSW_ATTN_LAUNCH
+}
+
 void launch_enc_attn(const h16* qkv, h16* out, int T, int H, int nb, hipStream_t s) {
     // 64-query blocks while 128-query ones would give < 2 workgroups per CU (OSW_ATTN_QB: force 64 / 128)
     static const int qb_env = [] {
@@ -316,8 +335,6 @@ void launch_enc_attn(const h16* qkv, h16* out, int T, int H, int nb, hipStream_t
         return e ? atoi(e) : 0;
     }();
     const bool small = qb_env ? qb_env == 64 : (int64_t)((T + QB - 1) / QB) * H * nb < 512;
-    const int nqb = small ? (T + 63) / 64 : (T + QB - 1) / QB;
-    const int nwg = nqb * H * nb;
     static const bool eager = [] {  // OSW_ATTN_LAZY=0: rescale O on every tile (A/B)
         const char* e = std::getenv("OSW_ATTN_LAZY");
         return e && e[0] == '0';
@@ -329,20 +346,11 @@ void launch_enc_attn(const h16* qkv, h16* out, int T, int H, int nb, hipStream_t
         if (const char* e = std::getenv("OSW_ATTN_GRID")) return std::max(8, atoi(e) / 8 * 8);
         return 1 << 30;
     }();
-    const int grid = std::min(nwg, cap);
     static const bool pipe = [] {  // OSW_ATTN_PIPE=1: the software-pipelined step (A/B)
         const char* e = std::getenv("OSW_ATTN_PIPE");
         return e && e[0] == '1';
     }();
-#define OSW_ATTN_LAUNCH(L, Q, P) enc_attn_kernel<L, Q, P><<<grid, 256, 0, s>>>(qkv, out, T, H, nb, nqb)
-    if (small) {
-        if (eager) pipe ? OSW_ATTN_LAUNCH(false, 1, true) : OSW_ATTN_LAUNCH(false, 1, false);
-        else pipe ? OSW_ATTN_LAUNCH(true, 1, true) : OSW_ATTN_LAUNCH(true, 1, false);
-    } else {
-        if (eager) pipe ? OSW_ATTN_LAUNCH(false, 2, true) : OSW_ATTN_LAUNCH(false, 2, false);
-        else pipe ? OSW_ATTN_LAUNCH(true, 2, true) : OSW_ATTN_LAUNCH(true, 2, false);
-    }
-#undef OSW_ATTN_LAUNCH
+    launch_enc_attn_form(qkv, out, T, H, nb, eager, small, pipe, cap, s);
 }
 
 }  // namespace osw

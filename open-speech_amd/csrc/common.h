@@ -171,5 +171,6 @@ int launch_gemm_skinny_gelu_tail(const GemmArgs& g, float* part, const ProArgs& 
 int launch_gemm_skinny_pro(const GemmArgs& g, int pro, const ProArgs& pa, bool direct, float* part, hipStream_t s,
                            bool select = false, bool attn_tail = false);
 void launch_layernorm(const float* x, int64_t M, int D, const float* g, const float* b, h16* y, hipStream_t s);
+bool layernorm_width_ok(int D);  // the widths launch_layernorm has a kernel for (it throws for any other)
 
 }  // namespace osw

@@ -4,6 +4,8 @@
 #include "common.h"
 
 #include <cstdlib>
+#include <stdexcept>
+#include <string>
 
 namespace osw {
 
@@ -135,7 +137,18 @@ void launch_layernorm(const float* x, int64_t M, int D, const float* g, const fl
         case 6: layernorm_kernel<6><<<grid, 256, 0, s>>>(x, M, D, g, b, y); break;
         case 8: layernorm_kernel<8><<<grid, 256, 0, s>>>(x, M, D, g, b, y); break;
         case 10: layernorm_kernel<10><<<grid, 256, 0, s>>>(x, M, D, g, b, y); break;
-        default: layernorm_kernel<10><<<grid, 256, 0, s>>>(x, M, D, g, b, y); break;  // guarded by host check
+        // no instantiation: a wider kernel would read and write past the rows (osw_create
+        // refuses these widths, layernorm_width_ok)
+        default: throw std::invalid_argument("launch_layernorm: no kernel for width " + std::to_string(D));
+    }
+}
+
+// the widths launch_layernorm serves: 128 x {1, 2, 3, 4, 6, 8, 10}
+bool layernorm_width_ok(int D) {
+    if (D <= 0 || D % 128) return false;
+    switch (D / 128) {
+        case 1: case 2: case 3: case 4: case 6: case 8: case 10: return true;
+        default: return false;
     }
 }
 

@@ -38,6 +38,8 @@ void launch_mel_window(const float*, const int64_t*, const int*, const int*, con
                        int, int, h16*, hipStream_t);
 void launch_mel_normalize(const float*, int64_t, int, int, const int*, int, float*, hipStream_t);
 void launch_enc_attn(const h16*, h16*, int, int, int, hipStream_t);
+void launch_enc_attn_form(const h16*, h16*, int, int, int, bool eager, bool small, bool pipe, int grid_cap,
+                          hipStream_t);
 void launch_init_uniform(void*, bool, int64_t, uint64_t, float, float, int64_t, int64_t, hipStream_t);
 uint64_t hash_stream_key(uint64_t, int64_t);
 void launch_dec_self_attn(const float*, int, const float*, h16*, h16*, const int*, int, int, int, h16*, int64_t,
@@ -2485,6 +2487,8 @@ int osw_create(const osw_dims* dims, int32_t device, int32_t max_batch, osw_ctx*
         REQUIRE(dims->n_text_ctx <= 448, "n_text_ctx must be <= 448");
         REQUIRE(dims->n_audio_state == dims->n_text_state, "encoder and decoder width must match");
         REQUIRE(dims->n_audio_state <= 1280, "model width > 1280 unsupported");
+        REQUIRE(layernorm_width_ok(dims->n_audio_state),
+                "model width must be one of 128, 256, 384, 512, 768, 1024, 1280 (no LayerNorm kernel for 640, 896, 1152)");
         int ndev = 0;
         HIPCHK(hipGetDeviceCount(&ndev));
         REQUIRE(device >= 0 && device < ndev, "device ordinal out of range");
@@ -3116,6 +3120,132 @@ int osw_debug_gemm(osw_ctx* c, int32_t M, int32_t N, int32_t K, int32_t variant,
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
         for (void* p : tmp) (void)hipFree(p);
+    });
+}
+
+namespace {
+// temporary device buffers of one debug call: freed when the call ends, however it ends
+struct TmpBufs {
+    std::vector<void*> v;
+    ~TmpBufs() {
+        GateLock gate_(capture_gate());
+        for (void* p : v) (void)hipFree(p);
+    }
+};
+}  // namespace
+
+int osw_debug_enc_attn(osw_ctx* c, const void* qkv, int32_t nb, int32_t H, int32_t form, void* out) {
+    return guard([&] {
+        REQUIRE(c && qkv && out, "null argument");
+        REQUIRE(nb >= 1 && nb <= 64 && H >= 1 && H <= 20, "encoder attention shape out of range");
+        REQUIRE(form >= 0 && form < 16 && (form == 0 || (form & 1)), "form: 0 (auto) or 1 | 2 eager | 4 128-query | 8 pipelined");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t n = (size_t)nb * H * T_ENC * 64;
+        h16* dq = dalloc<h16>(3 * n, tmp.v);
+        h16* dout = dalloc<h16>(n, tmp.v);
+        HIPCHK(hipMemcpyAsync(dq, qkv, 3 * n * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemsetAsync(dout, 0xff, n * 2, c->stream));  // NaN: an unwritten element shows
+        if (form == 0) launch_enc_attn(dq, dout, T_ENC, H, nb, c->stream);
+        else launch_enc_attn_form(dq, dout, T_ENC, H, nb, (form & 2) != 0, !(form & 4), (form & 8) != 0, 1 << 30, c->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, dout, n * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
+int osw_debug_dec_xattn(osw_ctx* c, const float* q_slabs, int32_t ks, const float* bias, const void* K, const void* V,
+                        int32_t rows, int32_t beam, int32_t legacy, float* out) {
+    return guard([&] {
+        REQUIRE(c && q_slabs && K && V && out, "null argument");
+        REQUIRE(ks >= 1 && ks <= 32, "ks out of range");
+        REQUIRE(beam >= 1 && beam <= MAX_BEAM && rows >= beam && rows % beam == 0, "rows must be windows x beam, beam <= 8");
+        const int H = c->d.n_text_head, D = c->d.n_text_state, W = rows / beam;
+        REQUIRE(W <= c->B, "more windows than the context's max_batch (its arrival tickets)");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t nq = (size_t)ks * rows * D, nkv = (size_t)W * H * T_ENC * 64, no = (size_t)rows * D;
+        float* dq = dalloc<float>(nq, tmp.v);
+        float* db = dalloc<float>(D, tmp.v);
+        h16* dk = dalloc<h16>(nkv, tmp.v);
+        h16* dv = dalloc<h16>(nkv, tmp.v);
+        h16* dout = dalloc<h16>(2 * no, tmp.v);  // hi, then lo
+        float* ws = legacy ? nullptr : dalloc<float>((size_t)rows * H * XCHUNKS * XPART, tmp.v);
+        SelState* st = dalloc<SelState>((size_t)rows, tmp.v);
+        HIPCHK(hipMemcpyAsync(dq, q_slabs, nq * 4, hipMemcpyHostToDevice, c->stream));
+        // the chunk kernels read the bias unconditionally: "none" is a zero bias for them
+        if (bias) HIPCHK(hipMemcpyAsync(db, bias, (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
+        else HIPCHK(hipMemsetAsync(db, 0, (size_t)D * 4, c->stream));
+        HIPCHK(hipMemcpyAsync(dk, K, nkv * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dv, V, nkv * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemsetAsync(dout, 0xff, 2 * no * 2, c->stream));
+        HIPCHK(hipMemsetAsync(st, 0, (size_t)rows * sizeof(SelState), c->stream));
+        launch_dec_cross_attn(dq, ks, (legacy && !bias) ? nullptr : db, dk, dv, rows, H, T_ENC, beam, dout, (int64_t)no, ws,
+                              c->xticket, st, c->stream);
+        hipError_t e = hipGetLastError();
+        // the tickets are zero between launches (the last arriver resets its own); after a
+        // failed launch they may not be, and the decode path shares them
+        hipError_t e2 = hipMemsetAsync(c->xticket, 0, (size_t)W * H * sizeof(int), c->stream);
+        HIPCHK(e);
+        HIPCHK(e2);
+        std::vector<h16> back(2 * no);
+        HIPCHK(hipMemcpyAsync(back.data(), dout, 2 * no * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < no; ++i) out[i] = (float)back[i] + (float)back[no + i];
+    });
+}
+
+int osw_debug_dec_self_attn(osw_ctx* c, const float* qkv_slabs, int32_t ks, const float* bias, void* kcache, void* vcache,
+                            int32_t rows, const int32_t* pos, int32_t pos_per_row, const int32_t* ancestry,
+                            int32_t group, float* out) {
+    return guard([&] {
+        REQUIRE(c && qkv_slabs && bias && kcache && vcache && pos && out, "null argument");
+        REQUIRE(ks >= 1 && ks <= 32, "ks out of range");
+        REQUIRE(rows >= 1 && rows <= 1024, "rows out of range");
+        const int H = c->d.n_text_head, D = c->d.n_text_state, ctx = c->d.n_text_ctx;
+        REQUIRE(ctx >= 1 && ctx <= 448, "n_text_ctx out of range");
+        for (int r = 0; r < (pos_per_row ? rows : 1); ++r) REQUIRE(pos[r] >= 0 && pos[r] < ctx, "position outside the cache");
+        if (ancestry) {
+            REQUIRE(group >= 1 && group <= MAX_BEAM && rows % group == 0, "rows must be windows x group, group <= 8");
+            for (size_t i = 0; i < (size_t)rows * ctx; ++i)
+                REQUIRE(ancestry[i] >= 0 && ancestry[i] < rows, "ancestry names a row outside the cache");
+        } else {
+            REQUIRE(group == 1, "group needs an ancestry table");
+        }
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t nq = (size_t)ks * rows * 3 * D, nkv = (size_t)rows * H * ctx * 64, no = (size_t)rows * D;
+        float* dq = dalloc<float>(nq, tmp.v);
+        float* db = dalloc<float>((size_t)3 * D, tmp.v);
+        h16* dk = dalloc<h16>(nkv, tmp.v);
+        h16* dv = dalloc<h16>(nkv, tmp.v);
+        h16* dout = dalloc<h16>(2 * no, tmp.v);
+        int* dpos = dalloc<int>((size_t)rows, tmp.v);
+        int* danc = ancestry ? dalloc<int>((size_t)rows * ctx, tmp.v) : nullptr;
+        SelState* st = dalloc<SelState>((size_t)rows, tmp.v);
+        HIPCHK(hipMemcpyAsync(dq, qkv_slabs, nq * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(db, bias, (size_t)3 * D * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dk, kcache, nkv * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dv, vcache, nkv * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dpos, pos, (size_t)(pos_per_row ? rows : 1) * 4, hipMemcpyHostToDevice, c->stream));
+        if (danc) HIPCHK(hipMemcpyAsync(danc, ancestry, (size_t)rows * ctx * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemsetAsync(dout, 0xff, 2 * no * 2, c->stream));
+        HIPCHK(hipMemsetAsync(st, 0, (size_t)rows * sizeof(SelState), c->stream));
+        launch_dec_self_attn(dq, ks, db, dk, dv, dpos, rows, H, ctx, dout, (int64_t)no, danc, group, st, c->stream,
+                             pos_per_row ? 1 : 0);
+        HIPCHK(hipGetLastError());
+        std::vector<h16> back(2 * no);
+        HIPCHK(hipMemcpyAsync(back.data(), dout, 2 * no * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(kcache, dk, nkv * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(vcache, dv, nkv * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < no; ++i) out[i] = (float)back[i] + (float)back[no + i];
     });
 }
 

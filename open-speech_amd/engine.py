@@ -518,6 +518,78 @@ class WhisperEngine:
                                            iters, C.byref(ms)), "osw_debug_gemm")
         return out, ms.value
 
+    ATTN_AUTO = 0
+
+    @staticmethod
+    def attn_form(eager: bool = False, qb128: bool = False, pipe: bool = False) -> int:
+        """An explicit encoder-attention form for debug_enc_attn (osw.h OSW_ATTN_FORM*)."""
+        return 1 | (2 if eager else 0) | (4 if qb128 else 0) | (8 if pipe else 0)
+
+    def debug_enc_attn(self, qkv: np.ndarray, form: int = 0) -> np.ndarray:
+        """One encoder-attention launch: qkv fp16 [3][nb][H][1500][64] -> fp16 [nb*1500][H*64]."""
+        qkv = np.ascontiguousarray(qkv, dtype=np.float16)
+        three, nb, H, T, hd = qkv.shape
+        if (three, T, hd) != (3, 1500, 64):
+            raise ValueError("qkv must be [3][nb][H][1500][64]")
+        out = np.empty((nb * T, H * hd), np.float16)
+        _lib.check(self.lib.osw_debug_enc_attn(self.ctx, qkv.ctypes.data_as(C.c_void_p), nb, H, int(form),
+                                               out.ctypes.data_as(C.c_void_p)), "osw_debug_enc_attn")
+        return out
+
+    def debug_dec_xattn(self, q_slabs: np.ndarray, bias, K: np.ndarray, V: np.ndarray, beam: int = 1,
+                        legacy: bool = False) -> np.ndarray:
+        """One decoder cross-attention launch: q_slabs fp32 [ks][rows][D], bias [D] or None, K and V
+        fp16 [W][H][1500][64], rows = W * beam -> fp32 [rows][D] (the hi + lo halves summed)."""
+        q = np.ascontiguousarray(q_slabs, dtype=np.float32)
+        K = np.ascontiguousarray(K, dtype=np.float16)
+        V = np.ascontiguousarray(V, dtype=np.float16)
+        ks, rows, Dm = q.shape
+        W, H = K.shape[:2]
+        if K.shape != (W, H, 1500, 64) or V.shape != K.shape or Dm != self.dims.n_text_state or \
+                H != self.dims.n_text_head or rows != W * beam:
+            raise ValueError("shapes: q [ks][W*beam][D], K/V [W][H][1500][64] with the engine's H and D")
+        b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+        if b is not None and b.shape != (Dm,):
+            raise ValueError("bias must be [D]")
+        out = np.empty((rows, Dm), np.float32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(self.lib.osw_debug_dec_xattn(self.ctx, q.ctypes.data_as(fp), ks,
+                                                None if b is None else b.ctypes.data_as(fp),
+                                                K.ctypes.data_as(C.c_void_p), V.ctypes.data_as(C.c_void_p), rows,
+                                                int(beam), int(bool(legacy)), out.ctypes.data_as(fp)),
+                   "osw_debug_dec_xattn")
+        return out
+
+    def debug_dec_self_attn(self, qkv_slabs: np.ndarray, bias: np.ndarray, kcache: np.ndarray, vcache: np.ndarray,
+                            pos, ancestry: np.ndarray | None = None, group: int = 1):
+        """One decoder self-attention launch: qkv_slabs fp32 [ks][rows][3D], bias [3D], caches fp16
+        [rows][H][ctx][64], pos an int or one per row, ancestry [rows][ctx] or None.  Returns
+        (out fp32 [rows][D], kcache, vcache) with the caches as the kernel left them (copies)."""
+        q = np.ascontiguousarray(qkv_slabs, dtype=np.float32)
+        ks, rows, D3 = q.shape
+        H, ctx, Dm = self.dims.n_text_head, self.dims.n_text_ctx, self.dims.n_text_state
+        kc = np.array(kcache, dtype=np.float16, order="C")
+        vc = np.array(vcache, dtype=np.float16, order="C")
+        b = np.ascontiguousarray(bias, dtype=np.float32)
+        if D3 != 3 * Dm or kc.shape != (rows, H, ctx, 64) or vc.shape != kc.shape or b.shape != (3 * Dm,):
+            raise ValueError("shapes: qkv [ks][rows][3D], bias [3D], caches [rows][H][ctx][64]")
+        per_row = not np.isscalar(pos)
+        p = np.ascontiguousarray(np.atleast_1d(pos), dtype=np.int32)
+        if per_row and p.shape != (rows,):
+            raise ValueError("one position per row")
+        anc = None
+        if ancestry is not None:
+            anc = np.ascontiguousarray(ancestry, dtype=np.int32)
+            if anc.shape != (rows, ctx):
+                raise ValueError("ancestry must be [rows][ctx]")
+        out = np.empty((rows, Dm), np.float32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(self.lib.osw_debug_dec_self_attn(self.ctx, q.ctypes.data_as(fp), ks, b.ctypes.data_as(fp),
+                                                    kc.ctypes.data_as(C.c_void_p), vc.ctypes.data_as(C.c_void_p),
+                                                    rows, _i32p(p), int(per_row), None if anc is None else _i32p(anc),
+                                                    int(group), out.ctypes.data_as(fp)), "osw_debug_dec_self_attn")
+        return out, kc, vc
+
     def hold_capture(self, hold_ms: int) -> None:
         """Test hook (osw_debug_hold_capture): hold a stream capture open on this context's
         stream for ``hold_ms`` under the decode-graph capture's locks; raises if the
