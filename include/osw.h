@@ -38,6 +38,9 @@
  *       stage-level read-back and the DTW kernel alone, used only by the parity tests
  *   osw_debug_enc_attn / osw_debug_dec_xattn / osw_debug_dec_self_attn
  *       one attention launch on host data, used only by the parity tests
+ *   osw_debug_dec_gemm / osw_debug_dec_resln / osw_debug_dec_gelu
+ *       one launch of the decoder's hi/lo GEMMs, residual+LayerNorm and GELU reduce on host
+ *       data, used only by the parity tests
  *   osw_decode_opts::repetition_penalty / no_repeat_ngram_size (+ osw_debug_history_rules)
  *       replace   WhisperModel.transcribe(..., repetition_penalty=, no_repeat_ngram_size=):
  *                 ctranslate2's RepetitionPenalty / NoRepeatNgram logits processors [upstream],
@@ -436,6 +439,47 @@ int osw_debug_dec_xattn(osw_ctx* ctx, const float* q_slabs, int32_t ks, const fl
 int osw_debug_dec_self_attn(osw_ctx* ctx, const float* qkv_slabs, int32_t ks, const float* bias, void* kcache,
                             void* vcache, int32_t rows, const int32_t* pos, int32_t pos_per_row,
                             const int32_t* ancestry, int32_t group, float* out);
+
+/* ---- the decoder's linear path, one production launcher per call on host data
+ * (parity tests: tests/test_gpu_dec_gemm.py; references and bounds: tests/dec_gemm_ref.py) ----
+ * Like the attention calls above: temporary device buffers, one launch through the launcher the
+ * decoder step uses, the result copied back.  Every precondition a launcher or kernel relies on is
+ * checked first and reported as an error (K and K / ksplit multiples of 128 for the skinny kernel,
+ * D % 4 == 0 and D <= 1280, the row limits of the fused prologues, the lo operand beyond 64 rows,
+ * the capacity of `out`).  `out` receives out_floats floats: the result first, the rest a guard
+ * band that the call fills with 0xff bytes before the launch, as it does the result's own floats,
+ * so an unwritten element and a store past the result both show.  *ks_out: the split count used.
+ *
+ * C = (A_hi + A_lo) · Wᵀ: A_hi, A_lo fp16 [M][K] (A_lo NULL: one fp16 operand, M <= 64), W fp16
+ * [N][K]; on the device the lo rows sit M rows after the hi rows with lda = K.  use_wf: W's
+ * fragment-major copy is packed (launch_frag_pack) and passed as GemmArgs::Wf.
+ *   form 0: launch_gemm_skinny_partial -> slabs [ks][M][N]
+ *   form 1: launch_gemm_tiled_partial with tiled_ksplit(M, N, K) -> slabs [ks][M][N]
+ *   form 2: the vocabulary projection as decoder_step runs it (the skinny kernel, split with
+ *           splitk_reduce_kernel or unsplit, or the wide kernel) -> [M][N], ldc = N */
+int osw_debug_dec_gemm(osw_ctx* ctx, int32_t form, int32_t M, int32_t N, int32_t K, const void* A_hi,
+                       const void* A_lo, const void* W, int32_t use_wf, float* out, int64_t out_floats,
+                       int32_t* ks_out);
+/* Residual update + LayerNorm of `rows` rows of width D: x' = x + bias + Σ slabs (slabs fp32
+ * [ks][rows][D], bias [D] or NULL), or with slabs == NULL the embedding entry x' = tok_emb[tok[r]]
+ * + pos_emb[pos] (tok_emb fp16 [V][D], pos_emb fp32 [ctx][D], tok [rows], pos [rows] when pos_row
+ * else [1]; ids are clamped into [0, V), positions to ctx - 1); y = LayerNorm(x') * gain + shift.
+ *   fused == 0: launch_dec_resid_ln.  x_out [rows][D] = x', y_hi / y_lo fp16 [rows][D] = the pair.
+ *   fused != 0 (rows <= 1): launch_gemm_skinny_pro(PRO_RESLN) with W fp16 [N][D]: x_out = x' (written
+ *     to a second buffer, as the fused step ping-pongs), x is read back from the device and must be
+ *     unchanged, and out = the GEMM's split-K slabs [ks][rows][N], or with direct != 0 C [rows][N]. */
+int osw_debug_dec_resln(osw_ctx* ctx, int32_t fused, int32_t direct, int32_t rows, int32_t D, const float* slabs,
+                        int32_t ks, const float* bias, float* x, const float* gain, const float* shift,
+                        const void* tok_emb, const float* pos_emb, const int32_t* tok, const int32_t* pos,
+                        int32_t ctx_len, int32_t V, int32_t pos_row, const void* W, int32_t N, int32_t use_wf,
+                        float* x_out, void* y_hi, void* y_lo, float* out, int64_t out_floats, int32_t* ks_out);
+/* GELU reduce y = gelu(bias + Σ slabs), slabs fp32 [ks][M][K4], bias [K4].
+ *   fused == 0: launch_dec_reduce_gelu -> the fp16 pair y_hi / y_lo [M][K4].
+ *   fused != 0 (M <= 8, K4 / ksplit <= 256): launch_gemm_skinny_pro(PRO_GELU) with W fp16 [N][K4]
+ *     -> out = its split-K slabs [ks][M][N]. */
+int osw_debug_dec_gelu(osw_ctx* ctx, int32_t fused, int32_t M, int32_t K4, const float* slabs, int32_t ks,
+                       const float* bias, const void* W, int32_t N, int32_t use_wf, void* y_hi, void* y_lo,
+                       float* out, int64_t out_floats, int32_t* ks_out);
 
 /* Test hook for the concurrency contract: holds a stream capture open on the context's
  * stream for hold_ms (under the same locks as a decode-graph capture) and fails if it was

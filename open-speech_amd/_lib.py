@@ -130,6 +130,17 @@ _SIGS = {
     "osw_debug_dec_self_attn": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, P(C.c_float), C.c_void_p, C.c_void_p,
                                           C.c_int32, P(C.c_int32), C.c_int32, P(C.c_int32), C.c_int32,
                                           P(C.c_float)]),
+    # one launch of the decoder's linear path on host data (parity tests)
+    "osw_debug_dec_gemm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int32, P(C.c_float), C.c_int64, P(C.c_int32)]),
+    "osw_debug_dec_resln": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), C.c_int32,
+                                      P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), C.c_void_p,
+                                      P(C.c_float), P(C.c_int32), P(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_void_p, C.c_int32, C.c_int32, P(C.c_float), C.c_void_p, C.c_void_p,
+                                      P(C.c_float), C.c_int64, P(C.c_int32)]),
+    "osw_debug_dec_gelu": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), C.c_int32,
+                                     P(C.c_float), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     P(C.c_float), C.c_int64, P(C.c_int32)]),
     "osw_debug_hold_capture": (C.c_int, [C.c_void_p, C.c_int32]),
     "osw_set_encoder_baton_min": (C.c_int, [C.c_void_p, C.c_int32]),
     "osw_set_profiling": (C.c_int, [C.c_void_p, C.c_int32]),

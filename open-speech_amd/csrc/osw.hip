@@ -3249,6 +3249,261 @@ int osw_debug_dec_self_attn(osw_ctx* c, const float* qkv_slabs, int32_t ks, cons
     });
 }
 
+namespace {
+// what launch_gemm_skinny_partial / launch_gemm_skinny_pro and gemm_skinny_kernel rely on: whole
+// 128-deep K ranges (the kernel's k32 steps come in fours, its chunk clamps assume kc >= 128)
+void require_skinny_split(int K, int ks) {
+    REQUIRE(K >= 128 && K % 128 == 0, "the skinny GEMM needs K a multiple of 128");
+    REQUIRE(ks >= 1 && K % ks == 0 && (K / ks) % 128 == 0, "the skinny GEMM needs K / ksplit a multiple of 128");
+}
+
+// W[N][K] (host fp16) on the device, with its fragment-major copy when asked for
+struct DebugW {
+    h16* w = nullptr;
+    h16* wf = nullptr;
+};
+void upload_w(osw_ctx* c, const void* W, int N, int K, bool use_wf, TmpBufs& tmp, DebugW& d) {
+    d.w = dalloc<h16>((size_t)N * K, tmp.v);
+    HIPCHK(hipMemcpyAsync(d.w, W, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
+    if (use_wf) {
+        d.wf = dalloc<h16>((size_t)((N + 15) / 16) * 16 * K, tmp.v);
+        launch_frag_pack(d.w, K, N, K, d.wf, c->stream);
+        HIPCHK(hipGetLastError());
+    }
+}
+
+// the fp32 result buffer of a debug call: out_floats floats of 0xff bytes (a NaN pattern), so an
+// element the kernel did not write, and a write past the `need` floats it owns, both show
+float* result_buf(osw_ctx* c, int64_t out_floats, TmpBufs& tmp) {
+    float* d = dalloc<float>((size_t)out_floats, tmp.v);
+    HIPCHK(hipMemsetAsync(d, 0xff, (size_t)out_floats * 4, c->stream));
+    return d;
+}
+}  // namespace
+
+int osw_debug_dec_gemm(osw_ctx* c, int32_t form, int32_t M, int32_t N, int32_t K, const void* A_hi, const void* A_lo,
+                       const void* W, int32_t use_wf, float* out, int64_t out_floats, int32_t* ks_out) {
+    return guard([&] {
+        REQUIRE(c && A_hi && W && out && ks_out, "null argument");
+        REQUIRE(form >= 0 && form <= 2, "form: 0 skinny slabs, 1 tiled slabs, 2 logits route");
+        REQUIRE(M >= 1 && M <= 1024 && N >= 1 && N <= 65536 && K >= 64 && K <= 8192, "GEMM shape out of range");
+        REQUIRE(A_lo || M <= 64, "more than 64 rows need the lo operand (32-row groups)");
+        int ks = 1;
+        bool skinny = true;
+        GemmArgs g = gemm_plain(nullptr, K, nullptr, nullptr, M, N, K, nullptr, N, EPI_F32);
+        if (form == 0) {
+            ks = skinny_ksplit(N, K);
+            require_skinny_split(K, ks);
+        } else if (form == 1) {
+            REQUIRE(A_lo, "the tiled split-K GEMM serves hi/lo decoder rows");
+            REQUIRE(K % 64 == 0 && N % 2 == 0, "the wide kernel needs K % 64 == 0 and an even N (8-byte stores)");
+            ks = tiled_ksplit(M, N, K);
+            REQUIRE(K % ks == 0 && (K / ks) % 64 == 0, "tiled split: K / ksplit a multiple of 64");
+            skinny = false;
+        } else {
+            skinny = skinny_ok(g);  // run_gemm's test (shape and epilogue only)
+            if (skinny) {
+                ks = skinny_ksplit(N, K);
+                require_skinny_split(K, ks);
+            } else {
+                REQUIRE(A_lo, "the logits route beyond the skinny kernel serves hi/lo rows");
+                REQUIRE(K % 64 == 0 && N % 2 == 0, "the wide kernel needs K % 64 == 0 and an even N (8-byte stores)");
+            }
+        }
+        const int64_t need = form == 2 ? (int64_t)M * N : (int64_t)ks * M * N;
+        REQUIRE(out_floats >= need && out_floats <= ((int64_t)1 << 27), "out_floats: the result's floats plus a guard band");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t na = (size_t)M * K;  // lo sits R = M rows after hi, as xdn / dattn / dh hold the pair
+        h16* dA = dalloc<h16>(2 * na, tmp.v);
+        HIPCHK(hipMemcpyAsync(dA, A_hi, na * 2, hipMemcpyHostToDevice, c->stream));
+        if (A_lo) HIPCHK(hipMemcpyAsync(dA + na, A_lo, na * 2, hipMemcpyHostToDevice, c->stream));
+        else HIPCHK(hipMemsetAsync(dA + na, 0, na * 2, c->stream));
+        DebugW dw;
+        upload_w(c, W, N, K, use_wf != 0, tmp, dw);
+        float* dout = result_buf(c, out_floats, tmp);
+        g.A = dA;
+        g.A_lo = A_lo ? dA + na : nullptr;
+        g.W = dw.w;
+        g.Wf = dw.wf;
+        if (form == 0) {
+            const int got = launch_gemm_skinny_partial(g, dout, c->stream);
+            REQUIRE(got == ks, "launch_gemm_skinny_partial chose another split");
+        } else if (form == 1) {
+            launch_gemm_tiled_partial(g, dout, ks, c->stream);
+        } else {
+            // decoder_step's logits GEMM: run_gemm's choice (with a workspace of this call's own)
+            g.C = dout;
+            g.share_cus = c->share_cus;
+            if (skinny) {
+                float* part = dalloc<float>((size_t)ks * M * N, tmp.v);
+                launch_gemm_skinny(g, part, c->stream);
+            } else {
+                launch_gemm(g, c->stream);
+            }
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, dout, (size_t)out_floats * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        *ks_out = ks;
+    });
+}
+
+int osw_debug_dec_resln(osw_ctx* c, int32_t fused, int32_t direct, int32_t rows, int32_t D, const float* slabs,
+                        int32_t ks, const float* bias, float* x, const float* gain, const float* shift,
+                        const void* tok_emb, const float* pos_emb, const int32_t* tok, const int32_t* pos, int32_t ctx,
+                        int32_t V, int32_t pos_row, const void* W, int32_t N, int32_t use_wf, float* x_out, void* y_hi,
+                        void* y_lo, float* out, int64_t out_floats, int32_t* ks_out) {
+    return guard([&] {
+        REQUIRE(c && x && gain && shift && x_out, "null argument");
+        REQUIRE(rows >= 1 && rows <= 64, "rows out of range");
+        REQUIRE(D >= 4 && D % 4 == 0 && D <= 1280, "LayerNorm width: a multiple of 4, at most 1280");
+        const bool embed = slabs == nullptr;
+        if (embed) {
+            REQUIRE(tok_emb && pos_emb && tok && pos, "the embedding entry needs tok_emb, pos_emb, tok and pos");
+            REQUIRE(V >= 1 && V <= 65536 && ctx >= 1 && ctx <= 448, "embedding tables out of range");
+            // (a token id is clamped into [0, V) by the kernel; a position only from above)
+            for (int r = 0; r < (pos_row ? rows : 1); ++r) REQUIRE(pos[r] >= 0, "negative position");
+        } else {
+            REQUIRE(ks >= 1 && ks <= 64, "ks out of range");
+        }
+        int gks = 1;
+        int64_t need = 0;
+        if (fused) {
+            REQUIRE(W && out && ks_out, "null argument");
+            REQUIRE(rows <= PRO_ROWS, "PRO_RESLN serves at most PRO_ROWS rows");
+            REQUIRE(N >= 1 && N <= 65536, "N out of range");
+            gks = direct ? 1 : skinny_ksplit(N, D);
+            require_skinny_split(D, gks);
+            need = (int64_t)gks * rows * N;
+            REQUIRE(out_floats >= need && out_floats <= ((int64_t)1 << 27), "out_floats: the result's floats plus a guard band");
+        } else {
+            REQUIRE(y_hi && y_lo, "null argument");
+        }
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t nx = (size_t)rows * D;
+        float* dx = dalloc<float>(nx, tmp.v);
+        float* dg = dalloc<float>(D, tmp.v);
+        float* db = dalloc<float>(D, tmp.v);
+        float* dbias = bias ? dalloc<float>(D, tmp.v) : nullptr;
+        float* dpart = nullptr;
+        h16* dte = nullptr;
+        float* dpe = nullptr;
+        int *dtok = nullptr, *dpos = nullptr;
+        HIPCHK(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dg, gain, (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(db, shift, (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
+        if (bias) HIPCHK(hipMemcpyAsync(dbias, bias, (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
+        if (embed) {
+            dte = dalloc<h16>((size_t)V * D, tmp.v);
+            dpe = dalloc<float>((size_t)ctx * D, tmp.v);
+            dtok = dalloc<int>((size_t)rows, tmp.v);
+            dpos = dalloc<int>((size_t)rows, tmp.v);
+            HIPCHK(hipMemcpyAsync(dte, tok_emb, (size_t)V * D * 2, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(dpe, pos_emb, (size_t)ctx * D * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(dtok, tok, (size_t)rows * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(dpos, pos, (size_t)(pos_row ? rows : 1) * 4, hipMemcpyHostToDevice, c->stream));
+        } else {
+            dpart = dalloc<float>((size_t)ks * nx, tmp.v);
+            HIPCHK(hipMemcpyAsync(dpart, slabs, (size_t)ks * nx * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        if (!fused) {
+            h16* dy = dalloc<h16>(2 * nx, tmp.v);  // hi, then lo
+            HIPCHK(hipMemsetAsync(dy, 0xff, 2 * nx * 2, c->stream));
+            launch_dec_resid_ln(dpart, ks, rows, D, dbias, dx, dg, db, dy, (int64_t)nx, dte, dpe, dtok, dpos, ctx, V,
+                                c->stream, pos_row ? 1 : 0);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(x_out, dx, nx * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(y_hi, dy, nx * 2, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(y_lo, dy + nx, nx * 2, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            return;
+        }
+        // the fused step's ping-pong: every workgroup reads x, one writes x' to the other buffer
+        float* dx2 = dalloc<float>(nx, tmp.v);
+        HIPCHK(hipMemsetAsync(dx2, 0xff, nx * 4, c->stream));
+        DebugW dw;
+        upload_w(c, W, N, D, use_wf != 0, tmp, dw);
+        float* dout = result_buf(c, out_floats, tmp);
+        GemmArgs g = gemm_plain(nullptr, D, dw.w, nullptr, rows, N, D, direct ? dout : nullptr, direct ? N : 0, EPI_F32);
+        g.Wf = dw.wf;
+        ProArgs pa{};
+        pa.ln = ResLnArgs{dpart, ks, (int64_t)nx, dbias, dx, dx2, dg, db, dte, dpe, dtok, dpos, ctx, D, V, pos_row ? 1 : 0};
+        const int got = launch_gemm_skinny_pro(g, PRO_RESLN, pa, direct != 0, direct ? nullptr : dout, c->stream);
+        HIPCHK(hipGetLastError());
+        REQUIRE(got == gks, "launch_gemm_skinny_pro chose another split");
+        HIPCHK(hipMemcpyAsync(x_out, dx2, nx * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(x, dx, nx * 4, hipMemcpyDeviceToHost, c->stream));  // must come back unchanged
+        HIPCHK(hipMemcpyAsync(out, dout, (size_t)out_floats * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        *ks_out = gks;
+    });
+}
+
+int osw_debug_dec_gelu(osw_ctx* c, int32_t fused, int32_t M, int32_t K4, const float* slabs, int32_t ks,
+                       const float* bias, const void* W, int32_t N, int32_t use_wf, void* y_hi, void* y_lo, float* out,
+                       int64_t out_floats, int32_t* ks_out) {
+    return guard([&] {
+        REQUIRE(c && slabs && bias, "null argument");
+        REQUIRE(M >= 1 && M <= 1024 && K4 >= 1 && K4 <= 8192, "shape out of range");
+        REQUIRE(ks >= 1 && ks <= 64, "ks out of range");
+        int gks = 1;
+        int64_t need = 0;
+        if (fused) {
+            REQUIRE(W && out && ks_out, "null argument");
+            REQUIRE(N >= 1 && N <= 65536, "N out of range");
+            REQUIRE(M <= GELU_ROWS, "PRO_GELU serves at most GELU_ROWS rows");
+            REQUIRE(K4 >= 128 && K4 % 128 == 0, "the skinny GEMM needs K a multiple of 128");
+            gks = skinny_ksplit(N, K4);
+            require_skinny_split(K4, gks);
+            REQUIRE(K4 / gks <= GELU_KC, "PRO_GELU: a workgroup's K range is at most GELU_KC deep");
+            need = (int64_t)gks * M * N;
+            REQUIRE(out_floats >= need && out_floats <= ((int64_t)1 << 27), "out_floats: the result's floats plus a guard band");
+        } else {
+            REQUIRE(y_hi && y_lo, "null argument");
+        }
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t n = (size_t)M * K4;
+        float* dpart = dalloc<float>((size_t)ks * n, tmp.v);
+        float* dbias = dalloc<float>(K4, tmp.v);
+        HIPCHK(hipMemcpyAsync(dpart, slabs, (size_t)ks * n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dbias, bias, (size_t)K4 * 4, hipMemcpyHostToDevice, c->stream));
+        if (!fused) {
+            h16* dy = dalloc<h16>(2 * n, tmp.v);  // hi, then lo
+            HIPCHK(hipMemsetAsync(dy, 0xff, 2 * n * 2, c->stream));
+            launch_dec_reduce_gelu(dpart, ks, M, K4, dbias, dy, (int64_t)n, c->stream);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(y_hi, dy, n * 2, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(y_lo, dy + n, n * 2, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            return;
+        }
+        DebugW dw;
+        upload_w(c, W, N, K4, use_wf != 0, tmp, dw);
+        float* dout = result_buf(c, out_floats, tmp);
+        GemmArgs g = gemm_plain(nullptr, K4, dw.w, nullptr, M, N, K4, nullptr, 0, EPI_F32);
+        g.Wf = dw.wf;
+        ProArgs pg{};
+        pg.part = dpart;
+        pg.ks = ks;
+        pg.bias = dbias;
+        const int got = launch_gemm_skinny_pro(g, PRO_GELU, pg, false, dout, c->stream);
+        HIPCHK(hipGetLastError());
+        REQUIRE(got == gks, "launch_gemm_skinny_pro chose another split");
+        HIPCHK(hipMemcpyAsync(out, dout, (size_t)out_floats * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        *ks_out = gks;
+    });
+}
+
 int osw_debug_hold_capture(osw_ctx* c, int32_t hold_ms) {
     return guard([&] {
         REQUIRE(c, "null ctx");

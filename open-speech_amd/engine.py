@@ -590,6 +590,125 @@ class WhisperEngine:
                                                     int(group), out.ctypes.data_as(fp)), "osw_debug_dec_self_attn")
         return out, kc, vc
 
+    DEBUG_GUARD = 256  # floats of guard band behind every fp32 result of the debug_dec_* calls
+
+    @staticmethod
+    def _guarded(raw: np.ndarray, shape) -> np.ndarray:
+        """The result part of a debug call's output; raises if the guard band behind it was written."""
+        n = int(np.prod(shape))
+        if not (raw[n:].view(np.uint32) == 0xFFFFFFFF).all():
+            raise AssertionError("a kernel wrote past its result (guard band changed)")
+        return raw[:n].reshape(shape).copy()
+
+    def debug_dec_gemm(self, form: int, A_hi: np.ndarray, A_lo, W: np.ndarray, use_wf: bool = False) -> np.ndarray:
+        """(A_hi + A_lo)·Wᵀ through a decoder GEMM launcher (osw_debug_dec_gemm): fp16 A_hi, A_lo [M][K]
+        (A_lo None: one operand), W [N][K].  form 0 / 1: fp32 slabs [ks][M][N] of the skinny / tiled
+        split-K launcher; form 2: the logits route's [M][N].  An element the kernel did not write is NaN."""
+        A_hi = np.ascontiguousarray(A_hi, dtype=np.float16)
+        W = np.ascontiguousarray(W, dtype=np.float16)
+        lo = None if A_lo is None else np.ascontiguousarray(A_lo, dtype=np.float16)
+        M, K = A_hi.shape
+        N = W.shape[0]
+        if W.shape != (N, K) or (lo is not None and lo.shape != (M, K)):
+            raise ValueError("shapes: A_hi, A_lo [M][K], W [N][K]")
+        # the launcher chooses the split (at most K / 64 slabs); what lies behind the result is guard band
+        raw = np.empty((1 if form == 2 else max(K // 64, 1)) * M * N + self.DEBUG_GUARD, np.float32)
+        ks = C.c_int32()
+        vp = C.c_void_p
+        _lib.check(self.lib.osw_debug_dec_gemm(self.ctx, int(form), M, N, K, A_hi.ctypes.data_as(vp),
+                                               None if lo is None else lo.ctypes.data_as(vp), W.ctypes.data_as(vp),
+                                               int(bool(use_wf)), raw.ctypes.data_as(C.POINTER(C.c_float)), raw.size,
+                                               C.byref(ks)), "osw_debug_dec_gemm")
+        return self._guarded(raw, (M, N) if form == 2 else (ks.value, M, N))
+
+    def debug_dec_resln(self, x, gain, shift, slabs=None, bias=None, embed=None, W=None, direct: bool = False,
+                        use_wf: bool = False):
+        """Residual update + LayerNorm (osw_debug_dec_resln).  x fp32 [rows][D]; slabs fp32 [ks][rows][D]
+        with bias [D] or None, or embed = (tok_emb fp16 [V][D], pos_emb fp32 [ctx][D], tok [rows], pos, pos_row)
+        for the embedding entry (pos [rows] when pos_row else one position).
+        W None: the standalone kernel; returns (x', y_hi, y_lo).
+        W fp16 [N][D]: the fused PRO_RESLN GEMM (one row); returns (x', out, x_after) with out the slabs
+        [ks][rows][N], or with direct C [rows][N], and x_after the input buffer as the kernel left it."""
+        x = np.array(x, dtype=np.float32, order="C")
+        rows, Dm = x.shape
+        fp, vp = C.POINTER(C.c_float), C.c_void_p
+        g = np.ascontiguousarray(gain, dtype=np.float32)
+        b = np.ascontiguousarray(shift, dtype=np.float32)
+        if g.shape != (Dm,) or b.shape != (Dm,):
+            raise ValueError("gain and shift must be [D]")
+        s = bi = te = pe = tk = ps = None
+        ks = ctx = V = pos_row = 0
+        if embed is None:
+            s = np.ascontiguousarray(slabs, dtype=np.float32)
+            ks = s.shape[0]
+            if s.shape != (ks, rows, Dm):
+                raise ValueError("slabs must be [ks][rows][D]")
+            if bias is not None:
+                bi = np.ascontiguousarray(bias, dtype=np.float32)
+                if bi.shape != (Dm,):
+                    raise ValueError("bias must be [D]")
+        else:
+            te, pe, tk, ps, pos_row = embed
+            te = np.ascontiguousarray(te, dtype=np.float16)
+            pe = np.ascontiguousarray(pe, dtype=np.float32)
+            tk = np.ascontiguousarray(tk, dtype=np.int32)
+            ps = np.ascontiguousarray(np.atleast_1d(ps), dtype=np.int32)
+            V, ctx = te.shape[0], pe.shape[0]
+            if te.shape != (V, Dm) or pe.shape != (ctx, Dm) or tk.shape != (rows,) or \
+                    ps.shape != ((rows,) if pos_row else (1,)):
+                raise ValueError("embed: tok_emb [V][D], pos_emb [ctx][D], tok [rows], pos [rows] or one")
+        ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        x_out = np.empty_like(x)
+        kso = C.c_int32()
+        if W is None:
+            hi, lo = np.empty((rows, Dm), np.float16), np.empty((rows, Dm), np.float16)
+            _lib.check(self.lib.osw_debug_dec_resln(self.ctx, 0, 0, rows, Dm, ptr(s, fp), ks, ptr(bi, fp), ptr(x, fp),
+                                                    ptr(g, fp), ptr(b, fp), ptr(te, vp), ptr(pe, fp),
+                                                    None if tk is None else _i32p(tk),
+                                                    None if ps is None else _i32p(ps), ctx, V, int(bool(pos_row)),
+                                                    None, 0, 0, ptr(x_out, fp), ptr(hi, vp), ptr(lo, vp), None, 0,
+                                                    C.byref(kso)), "osw_debug_dec_resln")
+            return x_out, hi, lo
+        W = np.ascontiguousarray(W, dtype=np.float16)
+        N = W.shape[0]
+        if W.shape != (N, Dm):
+            raise ValueError("W must be [N][D]")
+        raw = np.empty((1 if direct else max(Dm // 64, 1)) * rows * N + self.DEBUG_GUARD, np.float32)
+        _lib.check(self.lib.osw_debug_dec_resln(self.ctx, 1, int(bool(direct)), rows, Dm, ptr(s, fp), ks, ptr(bi, fp),
+                                                ptr(x, fp), ptr(g, fp), ptr(b, fp), ptr(te, vp), ptr(pe, fp),
+                                                None if tk is None else _i32p(tk), None if ps is None else _i32p(ps),
+                                                ctx, V, int(bool(pos_row)), ptr(W, vp), N, int(bool(use_wf)),
+                                                ptr(x_out, fp), None, None, ptr(raw, fp), raw.size, C.byref(kso)),
+                   "osw_debug_dec_resln")
+        return x_out, self._guarded(raw, (rows, N) if direct else (kso.value, rows, N)), x
+
+    def debug_dec_gelu(self, slabs, bias, W=None, use_wf: bool = False):
+        """GELU reduce gelu(bias + Σ slabs) (osw_debug_dec_gelu): slabs fp32 [ks][M][K4], bias [K4].
+        W None: the standalone kernel, returns the fp16 pair (y_hi, y_lo) [M][K4]; W fp16 [N][K4]: the
+        fused PRO_GELU GEMM, returns its slabs [ks'][M][N]."""
+        s = np.ascontiguousarray(slabs, dtype=np.float32)
+        ks, M, K4 = s.shape
+        bi = np.ascontiguousarray(bias, dtype=np.float32)
+        if bi.shape != (K4,):
+            raise ValueError("bias must be [K4]")
+        fp, vp = C.POINTER(C.c_float), C.c_void_p
+        kso = C.c_int32()
+        if W is None:
+            hi, lo = np.empty((M, K4), np.float16), np.empty((M, K4), np.float16)
+            _lib.check(self.lib.osw_debug_dec_gelu(self.ctx, 0, M, K4, s.ctypes.data_as(fp), ks, bi.ctypes.data_as(fp),
+                                                   None, 0, 0, hi.ctypes.data_as(vp), lo.ctypes.data_as(vp), None, 0,
+                                                   C.byref(kso)), "osw_debug_dec_gelu")
+            return hi, lo
+        W = np.ascontiguousarray(W, dtype=np.float16)
+        N = W.shape[0]
+        if W.shape != (N, K4):
+            raise ValueError("W must be [N][K4]")
+        raw = np.empty(max(K4 // 64, 1) * M * N + self.DEBUG_GUARD, np.float32)
+        _lib.check(self.lib.osw_debug_dec_gelu(self.ctx, 1, M, K4, s.ctypes.data_as(fp), ks, bi.ctypes.data_as(fp),
+                                               W.ctypes.data_as(vp), N, int(bool(use_wf)), None, None,
+                                               raw.ctypes.data_as(fp), raw.size, C.byref(kso)), "osw_debug_dec_gelu")
+        return self._guarded(raw, (kso.value, M, N))
+
     def hold_capture(self, hold_ms: int) -> None:
         """Test hook (osw_debug_hold_capture): hold a stream capture open on this context's
         stream for ``hold_ms`` under the decode-graph capture's locks; raises if the

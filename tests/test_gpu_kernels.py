@@ -1,8 +1,10 @@
 """Per-kernel GPU checks through the C ABI: every GEMM variant against a float64
-numpy reference on the same fp16 inputs (fp32 accumulation: |err| ~ 1e-3 relative)."""
+numpy reference on the same fp16 inputs, within G·S per element (S = |A|·|W|ᵀ; G is measured on
+a float32 restatement of the accumulation, tests/dec_gemm_ref.py)."""
 import numpy as np
 import pytest
 
+import dec_gemm_ref as R
 from open_speech_amd import dims as D
 from open_speech_amd.engine import WhisperEngine
 
@@ -35,8 +37,10 @@ def test_gemm_variants(eng, variant, M, N, K):
     W = rng.uniform(-1, 1, (N, K)).astype(np.float16)
     C, ms = eng.debug_gemm(A, W, variant)
     ref = A.astype(np.float64) @ W.astype(np.float64).T
-    err = np.abs(C - ref)
-    assert err.max() < 2e-3 * np.sqrt(K), (err.max(), ms)
+    S = np.abs(A).astype(np.float32) @ np.abs(W).astype(np.float32).T
+    ratio = float((np.abs(C - ref) / (R.G * S.astype(np.float64))).max())
+    print(f"variant {variant} {M}x{N}x{K}: worst |err| / (G S) = {ratio:.3f} (|err|/S = {ratio * R.G:.2e})")
+    assert ratio <= 1, (ratio, ms)
 
 
 @pytest.mark.parametrize("M,N,K", [(1500, 1280, 1280), (3000, 2304, 1280), (1500, 1280, 5120), (777, 264, 128)])
@@ -86,6 +90,12 @@ def test_8phase_transposed_epilogues_bit_identical(eng, M, N, K):
     gelu = 0.5 * ref * (1.0 + erf(ref / np.sqrt(2.0)))
     out = c8.view(np.float16).reshape(M, N).astype(np.float64)
     outg = c10.view(np.float16).reshape(M, N).astype(np.float64)
-    tol = 2e-3 * np.sqrt(K)
-    assert np.abs(out - ref).max() < tol + 1e-3 * np.abs(ref).max()
-    assert np.abs(outg - gelu).max() < tol + 1e-3 * np.abs(gelu).max()
+    # the fp32 value within G·S, then one fp16 rounding of it (2^-11 relative, 2^-25 in the
+    # subnormals); through the GELU the accumulation error grows by at most max |gelu'| = 1.13
+    # and erf_fast adds 0.5 |v| 1.5e-7
+    acc = R.G * (np.abs(A).astype(np.float32) @ np.abs(W).astype(np.float32).T).astype(np.float64)
+    r16 = lambda v: 2.0 ** -11 * np.abs(v) + 2.0 ** -25
+    r1 = float((np.abs(out - ref) / (acc + r16(ref))).max())
+    r2 = float((np.abs(outg - gelu) / (1.13 * acc + 0.5 * np.abs(ref) * R.ERF_FAST_ERR + r16(gelu))).max())
+    print(f"fp16 epilogues {M}x{N}x{K}: worst |err| / bound = {r1:.3f} (plain), {r2:.3f} (GELU)")
+    assert r1 <= 1 and r2 <= 1

@@ -39,7 +39,8 @@ def partial_launch(M, N, K, lo):   # launch_gemm_skinny_partial
 
 
 def kernel_consts(MT, LO):         # gemm_skinny_kernel<MT, ..., LO, PRO_NONE>
-    CK = (4 if MT == 3 else 2) if (LO and MT >= 2) else 8
+    # (<= 16 hi/lo rows: OSW_SKINNY_CK1 = 4 k32 steps per chunk; one operand: 8)
+    CK = (4 if MT == 3 else 2) if (LO and MT >= 2) else 4 if LO else 8
     CKK = CK * 32
     CPR = CKK // 8
     RPP = 64 // CPR
@@ -193,6 +194,27 @@ def test_skinny_partial_addressing(dims):
             if M > 64 and N > 1536:
                 continue   # > 64 rows and N > 1536: the tiled split-K GEMM, not this kernel (decoder_step)
             audit(M, N, K, True, R)
+
+
+# every (M, N, K, lo) tests/test_gpu_dec_gemm.py sends through gemm_skinny_kernel without a
+# prologue (osw_debug_dec_gemm lays lo M rows after hi: R = M): the partial slabs, the
+# one-operand groups of 48 and 64 rows, and the logits route's split and unsplit forms
+# (launch_gemm_skinny picks the same MT and split as partial_launch at <= 32 hi/lo rows)
+_FORM0_ROWS = (1, 5, 16, 17, 32, 33, 64, 65, 97)
+DEC_GEMM_TEST_SHAPES = (
+    [(M, N, K, True) for N, K in ((384, 384), (1280, 1280), (384, 1536)) for M in _FORM0_ROWS] +
+    [(M, 1280, 5120, True) for M in (1, 2, 3, 4, 5, 8, 33)] +
+    [(48, 384, 384, False), (64, 1280, 1280, False)] +
+    [(M, 1002, 384, True) for M in (1, 23)] +
+    [(M, 32730, 384, lo) for M in (1, 5, 23) for lo in (True, False)] +
+    [(1, 51866, 1280, True)] +
+    [(M, N, K, True) for N, K in ((1152, 384), (1280, 1280), (384, 1536)) for M in (1, 2, 3, 4, 5, 8)] +
+    [(65, 3840, 1280, True), (130, 1536, 1536, True)])
+
+
+@pytest.mark.parametrize("M,N,K,lo", DEC_GEMM_TEST_SHAPES)
+def test_dec_gemm_test_shapes_addressing(M, N, K, lo):
+    audit(M, N, K, lo, M)
 
 
 def test_kernel_constants_cover_rows():
