@@ -41,6 +41,9 @@
  *   osw_debug_dec_gemm / osw_debug_dec_resln / osw_debug_dec_gelu
  *       one launch of the decoder's hi/lo GEMMs, residual+LayerNorm and GELU reduce on host
  *       data, used only by the parity tests
+ *   osw_debug_enc_gemm / osw_debug_enc_layernorm
+ *       one launch of the encoder's tiled GEMM (any epilogue, grouped rows, head-major scatter)
+ *       and of its LayerNorm on host data, used only by the parity tests
  *   osw_decode_opts::repetition_penalty / no_repeat_ngram_size (+ osw_debug_history_rules)
  *       replace   WhisperModel.transcribe(..., repetition_penalty=, no_repeat_ngram_size=):
  *                 ctranslate2's RepetitionPenalty / NoRepeatNgram logits processors [upstream],
@@ -480,6 +483,58 @@ int osw_debug_dec_resln(osw_ctx* ctx, int32_t fused, int32_t direct, int32_t row
 int osw_debug_dec_gelu(osw_ctx* ctx, int32_t fused, int32_t M, int32_t K4, const float* slabs, int32_t ks,
                        const float* bias, const void* W, int32_t N, int32_t use_wf, void* y_hi, void* y_lo,
                        float* out, int64_t out_floats, int32_t* ks_out);
+
+/* ---- the encoder's tiled GEMM and LayerNorm, one launch per call on host data
+ * (parity tests: tests/test_gpu_enc_gemm.py; references and bounds: tests/enc_gemm_ref.py) ----
+ * One launch of the tiled GEMM family with the full argument set of the encoder's launches: grouped
+ * (overlapping) A rows, grouped C rows at an offset into their buffer, bias, the positional table,
+ * any of the six epilogues and the head-major scatter with slot redirection.  Row m of A is at
+ * A + (m / a_grp_rows) * a_grp_stride + (m % a_grp_rows) * lda and reads K elements; row m of C at
+ * C + c_offset + (m / c_grp_rows) * c_grp_stride + (m % c_grp_rows) * ldc (elements of the
+ * epilogue's type: fp16 for OSW_EPI_F16 / _F16_GELU / _HEADS, fp32 for the others).  OSW_EPI_HEADS
+ * writes fp16 [N / (64 heads_H)][heads_nb][heads_H][heads_T][64] at C + c_offset, row m = window *
+ * heads_T + t going to window heads_slot[window] (NULL: the window itself).
+ * The whole C buffer (c_bytes) is uploaded before the launch and downloaded after it, so the caller
+ * sees every byte the kernel did or did not touch (a canary; the residual of OSW_EPI_F32_RESID).
+ * variant: 0 the production chooser (with the context's current CU sharing), 1 the 128 tile double
+ * buffered, 2 the 256 tile, 4 the 8-phase 256 tile, 6 the 64 ring, 7 the 64 tile double buffered,
+ * 11 the 128 ring, 16 the half-width 256 x 128 tile.  hi/lo operands, split-K and fragment-major
+ * weights are not offered.
+ * Every precondition is checked before anything is launched (OSW_EINVAL): K % 64; lda and
+ * a_grp_stride multiples of 8; every A row inside a_count elements; every C row, or the head-major
+ * extent, inside c_bytes; C rows and groups that do not overlap (ldc >= N, c_grp_stride >=
+ * c_grp_rows * ldc); N, ldc and c_grp_stride multiples of 8 for every epilogue but OSW_EPI_F32
+ * (run_gemm's rule) and of 4 for OSW_EPI_F32 (the 256-row tiles store it in 16-B chunks too), c_offset
+ * a multiple of 8 (fp16) or 4 (fp32); pos [c_grp_rows][N] for OSW_EPI_F32_GELU_POS;
+ * N % (64 heads_H) == 0, M % heads_T == 0 and distinct slots < heads_nb for OSW_EPI_HEADS; variant
+ * 11 and 16 only where launch_gemm_variant would run the kernel they name. */
+#define OSW_EPI_F16 0
+#define OSW_EPI_F16_GELU 1
+#define OSW_EPI_F32_RESID 2
+#define OSW_EPI_F32_GELU_POS 3
+#define OSW_EPI_F32 4
+#define OSW_EPI_HEADS 5
+typedef struct osw_enc_gemm_desc {
+    int32_t M, N, K, variant, epi;
+    int32_t heads_T, heads_H, heads_nb;  /* OSW_EPI_HEADS */
+    int64_t lda, a_grp_rows, a_grp_stride;
+    int64_t a_count;                     /* fp16 elements of A */
+    int64_t ldc, c_grp_rows, c_grp_stride, c_offset;
+    int64_t c_bytes;                     /* bytes of C */
+    int64_t pos_count;                   /* floats of pos */
+    const void* A;                       /* fp16 [a_count] */
+    const void* W;                       /* fp16 [N][K] */
+    const float* bias;                   /* [N] or NULL */
+    const float* pos;                    /* [c_grp_rows][N], OSW_EPI_F32_GELU_POS */
+    const int32_t* heads_slot;           /* [M / heads_T] or NULL */
+    void* C;                             /* in/out */
+} osw_enc_gemm_desc;
+int osw_debug_enc_gemm(osw_ctx* ctx, const osw_enc_gemm_desc* desc);
+/* launch_layernorm on host data: y[m] = fp16(LayerNorm(x[m]) * gain + shift) for m < M, x fp32
+ * [M][D], y fp16 [M_alloc][D] in/out (uploaded first: rows M .. M_alloc-1 must come back unchanged).
+ * OSW_EINVAL for a width launch_layernorm has no kernel for. */
+int osw_debug_enc_layernorm(osw_ctx* ctx, int32_t M, int32_t M_alloc, int32_t D, const float* x, const float* gain,
+                            const float* shift, void* y);
 
 /* Test hook for the concurrency contract: holds a stream capture open on the context's
  * stream for hold_ms (under the same locks as a decode-graph capture) and fails if it was

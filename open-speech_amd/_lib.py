@@ -62,6 +62,14 @@ class osw_align_result(C.Structure):
     _fields_ = [("token_frame", C.POINTER(C.c_int32)), ("token_prob", C.POINTER(C.c_double)), ("stride", C.c_int32)]
 
 
+class osw_enc_gemm_desc(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("M", "N", "K", "variant", "epi", "heads_T", "heads_H", "heads_nb")] +
+                [(n, C.c_int64) for n in ("lda", "a_grp_rows", "a_grp_stride", "a_count", "ldc", "c_grp_rows",
+                                          "c_grp_stride", "c_offset", "c_bytes", "pos_count")] +
+                [("A", C.c_void_p), ("W", C.c_void_p), ("bias", C.POINTER(C.c_float)), ("pos", C.POINTER(C.c_float)),
+                 ("heads_slot", C.POINTER(C.c_int32)), ("C", C.c_void_p)])
+
+
 class osw_profile(C.Structure):
     _fields_ = [("mel_ms", C.c_double), ("encoder_ms", C.c_double), ("crosskv_ms", C.c_double),
                 ("decoder_ms", C.c_double), ("total_ms", C.c_double), ("decode_steps", C.c_int64),
@@ -141,6 +149,10 @@ _SIGS = {
     "osw_debug_dec_gelu": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), C.c_int32,
                                      P(C.c_float), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                      P(C.c_float), C.c_int64, P(C.c_int32)]),
+    # one launch of the encoder's tiled GEMM / LayerNorm on host data (parity tests)
+    "osw_debug_enc_gemm": (C.c_int, [C.c_void_p, P(osw_enc_gemm_desc)]),
+    "osw_debug_enc_layernorm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float),
+                                          P(C.c_float), C.c_void_p]),
     "osw_debug_hold_capture": (C.c_int, [C.c_void_p, C.c_int32]),
     "osw_set_encoder_baton_min": (C.c_int, [C.c_void_p, C.c_int32]),
     "osw_set_profiling": (C.c_int, [C.c_void_p, C.c_int32]),

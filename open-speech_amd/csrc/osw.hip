@@ -3504,6 +3504,149 @@ int osw_debug_dec_gelu(osw_ctx* c, int32_t fused, int32_t M, int32_t K4, const f
     });
 }
 
+namespace {
+// one past the farthest element that rows 0 .. M-1 of a grouped layout touch, each row `width`
+// elements wide (row m at (m / grp_rows) * grp_stride + (m % grp_rows) * ld): the last row of
+// every group is a candidate (a short last group may end before the one in front of it)
+int64_t grouped_extent(int64_t M, int64_t grp_rows, int64_t grp_stride, int64_t ld, int64_t width) {
+    int64_t end = 0;
+    for (int64_t q = 0; q * grp_rows < M; ++q) {
+        const int64_t rows = std::min(grp_rows, M - q * grp_rows);
+        end = std::max(end, q * grp_stride + (rows - 1) * ld + width);
+    }
+    return end;
+}
+}  // namespace
+
+int osw_debug_enc_gemm(osw_ctx* c, const osw_enc_gemm_desc* d) {
+    return guard([&] {
+        REQUIRE(c && d && d->A && d->W && d->C, "null argument");
+        const int M = d->M, N = d->N, K = d->K, epi = d->epi, variant = d->variant;
+        REQUIRE(M >= 1 && M <= 65536 && N >= 1 && N <= 8192 && K >= 64 && K <= 8192, "GEMM shape out of range");
+        REQUIRE(K % 64 == 0, "GEMM K must be a multiple of 64");
+        REQUIRE(epi >= EPI_F16 && epi <= EPI_HEADS, "epi: one of the six OSW_EPI_* epilogues");
+        REQUIRE(variant == 0 || variant == 1 || variant == 2 || variant == 4 || variant == 6 || variant == 7 ||
+                    variant == 11 || variant == 16,
+                "variant: 0 (chooser), 1, 2, 4, 6, 7, 11 or 16");
+        // A: 16-B pieces (global_load_lds), every row's K elements inside the buffer
+        REQUIRE(d->lda >= 0 && d->lda <= ((int64_t)1 << 24) && d->lda % 8 == 0, "lda: a multiple of 8 elements (16 B)");
+        REQUIRE(d->a_grp_rows >= 1 && d->a_grp_rows <= M, "a_grp_rows out of range");
+        REQUIRE(d->a_grp_stride >= 0 && d->a_grp_stride <= ((int64_t)1 << 31) && d->a_grp_stride % 8 == 0,
+                "a_grp_stride: a multiple of 8 elements (16 B)");
+        REQUIRE(d->a_count >= 1 && d->a_count <= ((int64_t)1 << 28), "a_count out of range");
+        REQUIRE(grouped_extent(M, d->a_grp_rows, d->a_grp_stride, d->lda, K) <= d->a_count,
+                "an A row reads past the A buffer");
+        // C
+        const bool heads = epi == EPI_HEADS;
+        const bool f32 = epi == EPI_F32_RESID || epi == EPI_F32_GELU_POS || epi == EPI_F32;
+        const int64_t esz = f32 ? 4 : 2;
+        REQUIRE(d->c_bytes >= esz && d->c_bytes <= ((int64_t)1 << 30) && d->c_bytes % esz == 0, "c_bytes out of range");
+        const int64_t c_count = d->c_bytes / esz;
+        REQUIRE(d->c_offset >= 0 && d->c_offset < c_count, "c_offset outside the C buffer");
+        REQUIRE(d->ldc >= 0 && d->ldc <= ((int64_t)1 << 24), "ldc out of range");
+        REQUIRE(d->c_grp_rows >= 1 && d->c_grp_rows <= M, "c_grp_rows out of range");
+        REQUIRE(d->c_grp_stride >= 0 && d->c_grp_stride <= ((int64_t)1 << 31), "c_grp_stride out of range");
+        if (f32) {
+            // f32x4 accesses of the staged fp32 epilogues (bias, residual, positional rows, stores);
+            // the plain fp32 store too, which the 256-row tiles stage the same way
+            REQUIRE(N % 4 == 0 && d->ldc % 4 == 0 && d->c_grp_stride % 4 == 0 && d->c_offset % 4 == 0,
+                    "fp32 epilogues need N, ldc, the C group stride and the C offset to be multiples of 4 (16-B rows)");
+            // the two fused fp32 epilogues as run_gemm serves them (the chooser's kernel depends on it)
+            REQUIRE(epi == EPI_F32 || (N % 8 == 0 && d->ldc % 8 == 0 && d->c_grp_stride % 8 == 0),
+                    "GEMM epilogue needs N, ldc and the C group stride to be multiples of 8");
+        } else {
+            // run_gemm's rule: 16-B chunks, only each chunk's first column is tested against N
+            REQUIRE(N % 8 == 0 && d->c_offset % 8 == 0 && (heads || (d->ldc % 8 == 0 && d->c_grp_stride % 8 == 0)),
+                    "GEMM epilogue needs N, ldc, the C group stride and the C offset to be multiples of 8");
+        }
+        int nwin = 0;
+        if (heads) {
+            REQUIRE(d->heads_T >= 1 && d->heads_H >= 1 && d->heads_H <= 64 && d->heads_nb >= 1 && d->heads_nb <= 1024,
+                    "head-major geometry out of range");
+            REQUIRE(N % (64 * d->heads_H) == 0, "EPI_HEADS needs N a multiple of 64 * heads_H");
+            REQUIRE(M % d->heads_T == 0, "EPI_HEADS needs M = windows * heads_T");
+            nwin = M / d->heads_T;
+            if (d->heads_slot) {
+                std::vector<char> seen(d->heads_nb, 0);
+                for (int i = 0; i < nwin; ++i) {
+                    const int sl = d->heads_slot[i];
+                    REQUIRE(sl >= 0 && sl < d->heads_nb && !seen[sl], "heads_slot: distinct slots < heads_nb");
+                    seen[sl] = 1;
+                }
+            } else {
+                REQUIRE(nwin <= d->heads_nb, "more windows than heads_nb");
+            }
+            const int64_t extent = (int64_t)(N / (64 * d->heads_H)) * d->heads_nb * d->heads_H * d->heads_T * 64;
+            REQUIRE(d->c_offset + extent <= c_count, "the head-major output does not fit the C buffer");
+        } else {
+            // rows and groups do not overlap in C (in-bounds stores that race; EPI_F32_RESID reads them too)
+            REQUIRE(d->ldc >= N || M == 1, "ldc shorter than a row");
+            REQUIRE(M <= d->c_grp_rows || d->c_grp_stride >= d->c_grp_rows * d->ldc, "C groups overlap");
+            REQUIRE(d->c_offset + grouped_extent(M, d->c_grp_rows, d->c_grp_stride, d->ldc, N) <= c_count,
+                    "a C row ends past the C buffer");
+        }
+        if (epi == EPI_F32_GELU_POS)
+            REQUIRE(d->pos && d->pos_count == d->c_grp_rows * (int64_t)N, "EPI_F32_GELU_POS needs pos [c_grp_rows][N]");
+        // an explicit variant must run the kernel it names (launch_gemm_variant falls through otherwise)
+        if (variant == 11)
+            REQUIRE(N % 8 == 0 && (heads || d->ldc % 8 == 0) && d->c_grp_stride % 8 == 0,
+                    "the 128 ring needs N, ldc and the C group stride to be multiples of 8");
+        if (variant == 16) REQUIRE(N % 8 == 0, "the half-width tile needs N % 8 == 0");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        h16* dA = dalloc<h16>((size_t)d->a_count, tmp.v);
+        h16* dW = dalloc<h16>((size_t)N * K, tmp.v);
+        char* dC = dalloc<char>((size_t)d->c_bytes, tmp.v);
+        float* dbias = d->bias ? dalloc<float>((size_t)N, tmp.v) : nullptr;
+        float* dpos = epi == EPI_F32_GELU_POS ? dalloc<float>((size_t)d->pos_count, tmp.v) : nullptr;
+        int* dslot = heads && d->heads_slot ? dalloc<int>((size_t)nwin, tmp.v) : nullptr;
+        HIPCHK(hipMemcpyAsync(dA, d->A, (size_t)d->a_count * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dW, d->W, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dC, d->C, (size_t)d->c_bytes, hipMemcpyHostToDevice, c->stream));
+        if (dbias) HIPCHK(hipMemcpyAsync(dbias, d->bias, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+        if (dpos) HIPCHK(hipMemcpyAsync(dpos, d->pos, (size_t)d->pos_count * 4, hipMemcpyHostToDevice, c->stream));
+        if (dslot) HIPCHK(hipMemcpyAsync(dslot, d->heads_slot, (size_t)nwin * 4, hipMemcpyHostToDevice, c->stream));
+        GemmArgs g{};
+        g.A = dA; g.lda = d->lda; g.a_grp_rows = d->a_grp_rows; g.a_grp_stride = d->a_grp_stride;
+        g.W = dW; g.ldw = K; g.bias = dbias; g.M = M; g.N = N; g.K = K;
+        g.C = dC + d->c_offset * esz; g.ldc = d->ldc; g.c_grp_rows = d->c_grp_rows; g.c_grp_stride = d->c_grp_stride;
+        g.pos = dpos; g.epi = epi;
+        g.heads_T = d->heads_T; g.heads_H = d->heads_H; g.heads_nb = d->heads_nb; g.heads_slot = dslot;
+        g.share_cus = c->share_cus;
+        launch_gemm_variant(g, variant, c->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(d->C, dC, (size_t)d->c_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
+int osw_debug_enc_layernorm(osw_ctx* c, int32_t M, int32_t M_alloc, int32_t D, const float* x, const float* gain,
+                            const float* shift, void* y) {
+    return guard([&] {
+        REQUIRE(c && x && gain && shift && y, "null argument");
+        REQUIRE(M >= 1 && M <= M_alloc && M_alloc <= 65536, "rows: 1 <= M <= M_alloc <= 65536");
+        REQUIRE(layernorm_width_ok(D), "no LayerNorm kernel for this width");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        float* dx = dalloc<float>((size_t)M * D, tmp.v);
+        float* dg = dalloc<float>((size_t)D, tmp.v);
+        float* db = dalloc<float>((size_t)D, tmp.v);
+        h16* dy = dalloc<h16>((size_t)M_alloc * D, tmp.v);
+        HIPCHK(hipMemcpyAsync(dx, x, (size_t)M * D * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dg, gain, (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(db, shift, (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dy, y, (size_t)M_alloc * D * 2, hipMemcpyHostToDevice, c->stream));
+        launch_layernorm(dx, M, D, dg, db, dy, c->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(y, dy, (size_t)M_alloc * D * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
 int osw_debug_hold_capture(osw_ctx* c, int32_t hold_ms) {
     return guard([&] {
         REQUIRE(c, "null ctx");

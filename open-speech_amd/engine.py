@@ -709,6 +709,71 @@ class WhisperEngine:
                                                raw.ctypes.data_as(fp), raw.size, C.byref(kso)), "osw_debug_dec_gelu")
         return self._guarded(raw, (kso.value, M, N))
 
+    EPI_F16, EPI_F16_GELU, EPI_F32_RESID, EPI_F32_GELU_POS, EPI_F32, EPI_HEADS = range(6)
+
+    def debug_enc_gemm(self, A: np.ndarray, W: np.ndarray, Cbuf: np.ndarray, *, M: int, epi: int, variant: int = 0,
+                       lda: int | None = None, a_grp_rows: int | None = None, a_grp_stride: int = 0,
+                       ldc: int | None = None, c_grp_rows: int | None = None, c_grp_stride: int = 0,
+                       c_offset: int = 0, bias=None, pos=None, heads=None, heads_slot=None) -> np.ndarray:
+        """One tiled encoder GEMM launch with the full argument set (osw_debug_enc_gemm): A a flat fp16
+        buffer whose row m starts at (m // a_grp_rows) * a_grp_stride + (m % a_grp_rows) * lda, W fp16
+        [N][K], Cbuf the whole output buffer (fp16 for EPI_F16 / EPI_F16_GELU / EPI_HEADS, fp32 for the
+        others) as it is before the launch; returns a copy of it as the kernel left it.  heads =
+        (heads_T, heads_H, heads_nb) for EPI_HEADS.  The library checks every precondition; this wrapper
+        only the sizes of the host arrays it hands over."""
+        A = np.ascontiguousarray(A, dtype=np.float16).ravel()
+        W = np.ascontiguousarray(W, dtype=np.float16)
+        N, K = W.shape
+        f16 = epi in (self.EPI_F16, self.EPI_F16_GELU, self.EPI_HEADS)
+        out = np.array(Cbuf, dtype=np.float16 if f16 else np.float32, order="C").ravel()
+        fp = C.POINTER(C.c_float)
+        d = _lib.osw_enc_gemm_desc()
+        d.M, d.N, d.K, d.variant, d.epi = int(M), N, K, int(variant), int(epi)
+        d.heads_T, d.heads_H, d.heads_nb = (int(v) for v in (heads or (0, 0, 0)))
+        d.lda = K if lda is None else int(lda)
+        d.a_grp_rows = int(M) if a_grp_rows is None else int(a_grp_rows)
+        d.a_grp_stride = int(a_grp_stride)
+        d.a_count = A.size
+        d.ldc = (0 if epi == self.EPI_HEADS else N) if ldc is None else int(ldc)
+        d.c_grp_rows = int(M) if c_grp_rows is None else int(c_grp_rows)
+        d.c_grp_stride, d.c_offset, d.c_bytes = int(c_grp_stride), int(c_offset), out.nbytes
+        d.A, d.W, d.C = A.ctypes.data, W.ctypes.data, out.ctypes.data
+        keep = [A, W, out]
+        if bias is not None:
+            b = np.ascontiguousarray(bias, dtype=np.float32)
+            if b.shape != (N,):
+                raise ValueError("bias must be [N]")
+            d.bias = b.ctypes.data_as(fp)
+            keep.append(b)
+        if pos is not None:
+            p = np.ascontiguousarray(pos, dtype=np.float32)
+            d.pos, d.pos_count = p.ctypes.data_as(fp), p.size
+            keep.append(p)
+        if heads_slot is not None:
+            sl = np.ascontiguousarray(heads_slot, dtype=np.int32)
+            if d.heads_T < 1 or sl.shape != (int(M) // d.heads_T,):
+                raise ValueError("heads_slot must hold one slot per window")
+            d.heads_slot = _i32p(sl)
+            keep.append(sl)
+        _lib.check(self.lib.osw_debug_enc_gemm(self.ctx, C.byref(d)), "osw_debug_enc_gemm")
+        return out
+
+    def debug_enc_layernorm(self, x: np.ndarray, gain, shift, y: np.ndarray) -> np.ndarray:
+        """The encoder's LayerNorm (osw_debug_enc_layernorm) on x fp32 [M][D]: y fp16 [M_alloc][D] is the
+        output buffer as it is before the launch (M_alloc >= M); returns a copy as the kernel left it."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        M, Dm = x.shape
+        g = np.ascontiguousarray(gain, dtype=np.float32)
+        b = np.ascontiguousarray(shift, dtype=np.float32)
+        out = np.array(y, dtype=np.float16, order="C")
+        if g.shape != (Dm,) or b.shape != (Dm,) or out.ndim != 2 or out.shape[1] != Dm:
+            raise ValueError("shapes: x [M][D], gain and shift [D], y [M_alloc][D]")
+        fp = C.POINTER(C.c_float)
+        _lib.check(self.lib.osw_debug_enc_layernorm(self.ctx, M, out.shape[0], Dm, x.ctypes.data_as(fp),
+                                                    g.ctypes.data_as(fp), b.ctypes.data_as(fp),
+                                                    out.ctypes.data_as(C.c_void_p)), "osw_debug_enc_layernorm")
+        return out
+
     def hold_capture(self, hold_ms: int) -> None:
         """Test hook (osw_debug_hold_capture): hold a stream capture open on this context's
         stream for ``hold_ms`` under the decode-graph capture's locks; raises if the

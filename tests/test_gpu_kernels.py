@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import dec_gemm_ref as R
+import enc_gemm_ref as E
 from open_speech_amd import dims as D
 from open_speech_amd.engine import WhisperEngine
 
@@ -94,8 +95,8 @@ def test_8phase_transposed_epilogues_bit_identical(eng, M, N, K):
     # subnormals); through the GELU the accumulation error grows by at most max |gelu'| = 1.13
     # and erf_fast adds 0.5 |v| 1.5e-7
     acc = R.G * (np.abs(A).astype(np.float32) @ np.abs(W).astype(np.float32).T).astype(np.float64)
-    r16 = lambda v: 2.0 ** -11 * np.abs(v) + 2.0 ** -25
-    r1 = float((np.abs(out - ref) / (acc + r16(ref))).max())
-    r2 = float((np.abs(outg - gelu) / (1.13 * acc + 0.5 * np.abs(ref) * R.ERF_FAST_ERR + r16(gelu))).max())
+    # (enc_gemm_ref.f16_bound / gelu_f16_bound: the same terms, shared with tests/test_gpu_enc_gemm.py)
+    r1 = float((np.abs(out - ref) / E.f16_bound(acc, ref)).max())
+    r2 = float((np.abs(outg - gelu) / E.gelu_f16_bound(acc, ref, gelu)).max())
     print(f"fp16 epilogues {M}x{N}x{K}: worst |err| / bound = {r1:.3f} (plain), {r2:.3f} (GELU)")
     assert r1 <= 1 and r2 <= 1
