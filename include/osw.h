@@ -55,6 +55,11 @@
  *                 language_probability / all_language_probs and WhisperModel.detect_language()
  *                 -> ctranslate2 Whisper.detect_language(encoder_output) [upstream]; the reference
  *                 reads none of them and hard-codes its confidences (src/streaming.py:407,419)
+ *   osw_decode_window_list (+ osw_debug_dec_xattn_windows)
+ *       replaces  the re-decode inside faster-whisper's generate_with_fallback [upstream]: a
+ *                 window that failed its compression-ratio or log-probability test is generated
+ *                 again at the next temperature from the encoder output it already has; the
+ *                 reference passes one scalar temperature (src/backends/faster_whisper.py:238)
  *
  * Conventions: every call returns 0 (OSW_OK) or a negative code; the message of
  * the last failure on the calling thread is osw_last_error().  Host buffers are
@@ -244,6 +249,19 @@ int osw_get_encoder_output(osw_ctx* ctx, int32_t window, float* out, int64_t out
  * all three modes. */
 int osw_decode_windows(osw_ctx* ctx, int32_t n, const osw_decode_opts* opts, osw_window_result* res);
 
+/* Decode of n of the windows last encoded: windows[i] indexes the last osw_encode_windows call,
+ * the indices distinct and in range, 1 <= n <= that call's window count (else OSW_EINVAL, before
+ * any launch; OSW_EINVAL too while a session is open).  Entry i of every per-window array of
+ * `opts` (prefix_tokens, language_tokens, token_budget) and of `res`, and confidence result i,
+ * belong to windows[i]; decoder rows are i * group + k.  The result is bit for bit what
+ * osw_decode_windows(n) returns after encoding just these windows in this order, in every mode,
+ * the same seed giving the same draws.  The call reads the cross-K/V where it lies and writes
+ * neither it nor the encoder output; the encode call's window count stays, so a later
+ * osw_decode_windows, osw_detect_language or osw_align_windows (with the original window
+ * indices) returns what it would have returned without this call. */
+int osw_decode_window_list(osw_ctx* ctx, int32_t n, const int32_t* windows, const osw_decode_opts* opts,
+                           osw_window_result* res);
+
 /* mel + encode + decode (greedy, beam search or sampling per `opts`, as
  * osw_decode_windows) of window 0 (seek 0, min(frames, 3000)) of every clip. */
 int osw_transcribe_batch(osw_ctx* ctx, const int16_t* pcm, const int64_t* offsets, int32_t n_clips,
@@ -432,6 +450,13 @@ int osw_debug_enc_attn(osw_ctx* ctx, const void* qkv, int32_t nb, int32_t H, int
  * beam > 1 with ks <= 8 the MFMA form.  The context's arrival tickets it used are zero on return. */
 int osw_debug_dec_xattn(osw_ctx* ctx, const float* q_slabs, int32_t ks, const float* bias, const void* K,
                         const void* V, int32_t rows, int32_t beam, int32_t legacy, float* out);
+/* The same launch with a window map (osw_decode_window_list's form): K and V fp16
+ * [kv_windows][H][1500][64], kv_windows <= max_batch, and row group w (rows w * beam .. + beam - 1)
+ * attends window window_map[w]; window_map holds rows / beam distinct indices below kv_windows (else
+ * OSW_EINVAL).  Equals osw_debug_dec_xattn over K[window_map], V[window_map] bit for bit. */
+int osw_debug_dec_xattn_windows(osw_ctx* ctx, const float* q_slabs, int32_t ks, const float* bias, const void* K,
+                                const void* V, int32_t kv_windows, const int32_t* window_map, int32_t rows,
+                                int32_t beam, int32_t legacy, float* out);
 /* Decoder self-attention step of `rows` rows with the context's H, D and ctx = n_text_ctx:
  * qkv_slabs fp32 [ks][rows][3 D] are the qkv projection's split-K partials, bias [3 D]; kcache and
  * vcache fp16 [rows][H][ctx][64] are read, get fp16(k) and fp16(v) of row r written at position

@@ -100,6 +100,9 @@ _SIGS = {
     "osw_encode_windows": (C.c_int, [C.c_void_p, P(osw_window), C.c_int32]),
     "osw_get_encoder_output": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), C.c_int64]),
     "osw_decode_windows": (C.c_int, [C.c_void_p, C.c_int32, P(osw_decode_opts), P(osw_window_result)]),
+    # a re-decode of some of the encoded windows (faster-whisper's generate_with_fallback retries)
+    "osw_decode_window_list": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_int32), P(osw_decode_opts),
+                                         P(osw_window_result)]),
     "osw_transcribe_batch": (C.c_int, [C.c_void_p, C.c_void_p, P(C.c_int64), C.c_int32, C.c_int32,
                                        P(osw_decode_opts), P(osw_window_result)]),
     "osw_transcribe_refill": (C.c_int, [C.c_void_p, C.c_void_p, P(C.c_int64), C.c_int32, C.c_int32,
@@ -135,6 +138,9 @@ _SIGS = {
     "osw_debug_enc_attn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "osw_debug_dec_xattn": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, P(C.c_float), C.c_void_p, C.c_void_p,
                                       C.c_int32, C.c_int32, C.c_int32, P(C.c_float)]),
+    "osw_debug_dec_xattn_windows": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, P(C.c_float), C.c_void_p,
+                                              C.c_void_p, C.c_int32, P(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                              P(C.c_float)]),
     "osw_debug_dec_self_attn": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, P(C.c_float), C.c_void_p, C.c_void_p,
                                           C.c_int32, P(C.c_int32), C.c_int32, P(C.c_int32), C.c_int32,
                                           P(C.c_float)]),

@@ -28,6 +28,8 @@ import time
 from pathlib import Path
 from typing import Any
 
+import numpy as np
+
 from . import model_store
 from .audio import decode_audio_bytes
 from .runner import BatchRunner
@@ -259,10 +261,12 @@ class HipWhisperBackend:
         return self._models[model_id]
 
     def _run_inference(self, audio: bytes, model_id: str, task: str = "transcribe", language: str | None = None,
-                       response_format: str = "json", temperature: float = 0.0,
+                       response_format: str = "json", temperature=0.0,
                        prompt: str | None = None, word_timestamps: bool | None = None,
                        timestamp_granularities: list | None = None, repetition_penalty: float | None = None,
-                       no_repeat_ngram_size: int | None = None, include: list | None = None) -> dict[str, Any]:
+                       no_repeat_ngram_size: int | None = None, include: list | None = None,
+                       compression_ratio_threshold: float | None = None,
+                       log_prob_threshold: float | None = None) -> dict[str, Any]:
         m = self._ensure_model(model_id)
         # OpenAI's include[]=logprobs; callers that pass nothing (the unchanged router) get the
         # STT_HIP_LOGPROBS default
@@ -284,7 +288,10 @@ class HipWhisperBackend:
             no_repeat_ngram_size = int(os.environ.get("STT_HIP_NO_REPEAT_NGRAM_SIZE", "0"))
         pcm = decode_audio_bytes(audio)
         opts = TranscribeOptions(task=task, language=language if (language and task == "transcribe") else None,
-                                 initial_prompt=prompt or None, temperature=float(temperature or 0.0),
+                                 initial_prompt=prompt or None, temperature=fallback_temperatures(temperature),
+                                 compression_ratio_threshold=2.4 if compression_ratio_threshold is None
+                                 else float(compression_ratio_threshold),
+                                 log_prob_threshold=-1.0 if log_prob_threshold is None else float(log_prob_threshold),
                                  beam_size=int(os.environ.get("STT_HIP_BEAM_SIZE", "5")),
                                  best_of=int(os.environ.get("STT_HIP_BEST_OF", "5")),
                                  tokens_per_second=self._length_control, word_timestamps=words,
@@ -303,22 +310,49 @@ class HipWhisperBackend:
                 "all_language_probs": res.all_language_probs}
 
     def transcribe(self, audio: bytes, model: str, language: str | None = None, response_format: str = "json",
-                   temperature: float = 0.0, prompt: str | None = None, word_timestamps: bool | None = None,
+                   temperature=0.0, prompt: str | None = None, word_timestamps: bool | None = None,
                    timestamp_granularities: list | None = None, repetition_penalty: float | None = None,
-                   no_repeat_ngram_size: int | None = None, include: list | None = None) -> dict[str, Any]:
+                   no_repeat_ngram_size: int | None = None, include: list | None = None,
+                   compression_ratio_threshold: float | None = None,
+                   log_prob_threshold: float | None = None) -> dict[str, Any]:
+        """``temperature``: a float (the reference's call) or a sequence, faster-whisper's fallback
+        ladder; ``compression_ratio_threshold`` / ``log_prob_threshold``: its retry tests (None:
+        faster-whisper's defaults 2.4 and -1.0)."""
         return self._run_inference(audio, model, task="transcribe", language=language, include=include,
+                                   compression_ratio_threshold=compression_ratio_threshold,
+                                   log_prob_threshold=log_prob_threshold,
                                    response_format=response_format, temperature=temperature, prompt=prompt,
                                    word_timestamps=word_timestamps, timestamp_granularities=timestamp_granularities,
                                    repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
 
-    def translate(self, audio: bytes, model: str, response_format: str = "json", temperature: float = 0.0,
+    def translate(self, audio: bytes, model: str, response_format: str = "json", temperature=0.0,
                   prompt: str | None = None, word_timestamps: bool | None = None,
                   timestamp_granularities: list | None = None, repetition_penalty: float | None = None,
-                  no_repeat_ngram_size: int | None = None, include: list | None = None) -> dict[str, Any]:
+                  no_repeat_ngram_size: int | None = None, include: list | None = None,
+                  compression_ratio_threshold: float | None = None,
+                  log_prob_threshold: float | None = None) -> dict[str, Any]:
         return self._run_inference(audio, model, task="translate", response_format=response_format, include=include,
+                                   compression_ratio_threshold=compression_ratio_threshold,
+                                   log_prob_threshold=log_prob_threshold,
                                    temperature=temperature, prompt=prompt, word_timestamps=word_timestamps,
                                    timestamp_granularities=timestamp_granularities,
                                    repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
+
+
+def fallback_temperatures(temperature):
+    """The ``TranscribeOptions.temperature`` of a request: a sequence is passed through
+    (faster-whisper's ladder); a scalar t stays a scalar, the reference's behaviour, unless
+    ``STT_HIP_TEMPERATURE_INCREMENT_ON_FALLBACK`` = x > 0, which makes it t, t + x, ... <= 1.0
+    (openai-whisper's CLI rule ``np.arange(t, 1.0 + 1e-6, x)``; unset or 0: off)."""
+    if temperature is not None and not isinstance(temperature, (str, bytes)) and hasattr(temperature, "__iter__"):
+        return tuple(float(t) for t in temperature)
+    t = float(temperature or 0.0)
+    inc = float(os.environ.get("STT_HIP_TEMPERATURE_INCREMENT_ON_FALLBACK", "0") or 0)
+    if inc > 0:
+        ladder = tuple(float(x) for x in np.arange(t, 1.0 + 1e-6, inc))
+        if len(ladder) > 1:
+            return ladder
+    return t
 
 
 def _default_engine_factory(dims, gpu: int, max_batch: int):

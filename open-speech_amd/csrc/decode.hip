@@ -96,11 +96,16 @@ __global__ __launch_bounds__(256) void dec_self_attn_kernel(const float* __restr
 // + bias; row b attends window b / beam: K at ((w*H + h)*T*64) of xk, V likewise.
 // Workgroups are remapped XCD-contiguously with the beam rows of one (window, head)
 // adjacent, so those rows' reads of the same 384 KB K/V share one L2.
+// wmap (all three cross-attention kernels; osw_decode_window_list): row group w attends the
+// K/V of window wmap[w] of the encode call, one uniform load per workgroup; null = identity.
+// Only the K/V head offset goes through the map: rows, done flags, tickets, the workspace
+// and the workgroup -> XCD placement keep w, so a mapped launch computes, group by group,
+// the bits of a plain launch over K[wmap], V[wmap].
 __global__ __launch_bounds__(256) void dec_cross_attn_kernel(const float* __restrict__ part, int ks,
                                                              const float* __restrict__ bias,
                                                              const h16* __restrict__ xk, const h16* __restrict__ xv,
                                                              int H, int B, int T, int beam, h16* __restrict__ out,
-                                                             int64_t lo_off) {
+                                                             int64_t lo_off, const int* __restrict__ wmap) {
     __shared__ h16 q16[HD];
     __shared__ float red4[256];
     const int nwg = gridDim.x, bid = blockIdx.x;
@@ -110,7 +115,7 @@ __global__ __launch_bounds__(256) void dec_cross_attn_kernel(const float* __rest
     const int b = w * beam + k;
     const int D = H * HD;
     reduce_head(part, ks, (int64_t)B * D, (int64_t)b * D + h * HD, bias, h * HD, q16, red4);
-    const int64_t hoff = ((int64_t)w * H + h) * T * HD;
+    const int64_t hoff = ((int64_t)(wmap ? wmap[w] : w) * H + h) * T * HD;
     attend_one<1536>(q16, xk + hoff, xv + hoff, T, out + (int64_t)b * D + h * HD, lo_off);
 }
 
@@ -181,7 +186,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 5 ? 4 
                                                               const h16* __restrict__ xk, const h16* __restrict__ xv,
                                                               int H, int W, int T, int beam, float* __restrict__ ws,
                                                               int* __restrict__ ticket, h16* __restrict__ out,
-                                                              int64_t lo_off, const SelState* __restrict__ st) {
+                                                              int64_t lo_off, const SelState* __restrict__ st,
+                                                              const int* __restrict__ wmap) {
     __shared__ float red[4][NB][HD];
     __shared__ __attribute__((aligned(16))) float pvs[NB > 1 ? 4 : 1][8][HD];  // beam rows' P·V reduction image
     __shared__ float rm[4][NB], rl[4][NB];
@@ -204,7 +210,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 5 ? 4 
     const int D = H * HD;
     const int per = (T + XCH - 1) / XCH;
     const int k0 = chunk * per, nk = min(T, k0 + per) - k0;
-    const int64_t hoff = ((int64_t)w * H + h) * T * HD;
+    const int64_t hoff = ((int64_t)(wmap ? wmap[w] : w) * H + h) * T * HD;  // K/V of window wmap[w]; all else keeps w
     // q of row r0 + k: fp16(bias + Σ split-K partials) / sqrt(64), the order of reduce_head
     // (wave wv: slabs wv, wv+4 pairwise by 8).  With ks <= 8 the wave's two slabs and the
     // bias are issued before the K/V stream, so the q reduction waits for them alone.
@@ -402,7 +408,8 @@ __global__ __launch_bounds__(256) void dec_xattn_mfma_kernel(const float* __rest
                                                              const h16* __restrict__ xk, const h16* __restrict__ xv,
                                                              int H, int W, int T, int beam, float* __restrict__ ws,
                                                              int* __restrict__ ticket, h16* __restrict__ out,
-                                                             int64_t lo_off, const SelState* __restrict__ st) {
+                                                             int64_t lo_off, const SelState* __restrict__ st,
+                                                             const int* __restrict__ wmap) {
     static_assert(NB <= 16 && XKEYS == 192, "16 MFMA columns; 4 waves x 3 key tiles");
     __shared__ __attribute__((aligned(16))) h16 Vl[XKEYS * HD];
     __shared__ __attribute__((aligned(16))) h16 qsh[16][HD];
@@ -425,7 +432,7 @@ __global__ __launch_bounds__(256) void dec_xattn_mfma_kernel(const float* __rest
     const int D = H * HD;
     const int per = (T + XCH - 1) / XCH;
     const int k0 = chunk * per, nk = min(T, k0 + per) - k0;
-    const int64_t hoff = ((int64_t)w * H + h) * T * HD;
+    const int64_t hoff = ((int64_t)(wmap ? wmap[w] : w) * H + h) * T * HD;  // K/V of window wmap[w]; all else keeps w
     // q of row r0 + k: fp16(bias + Σ split-K partials), the VALU kernel's order (ks <= 8:
     // wave wv holds slabs wv and wv + 4).  The slab loads go out first and all at once;
     // the K/V loads follow, and the barriers before the scores are raw s_barriers: vmcnt
@@ -1494,10 +1501,10 @@ void launch_dec_self_attn(const float* part, int ks, const float* bias, h16* kc,
 
 void launch_dec_cross_attn(const float* part, int ks, const float* bias, const h16* xk, const h16* xv, int B, int H,
                            int T, int beam, h16* out, int64_t lo_off, float* ws, int* ticket, const SelState* st,
-                           hipStream_t s) {
+                           hipStream_t s, const int* wmap) {
     static const bool legacy = std::getenv("OSW_XATTN_LEGACY") != nullptr;  // A/B switch: one workgroup per (row, head)
     if (legacy || !ws) {
-        dec_cross_attn_kernel<<<H * B, 256, 0, s>>>(part, ks, bias, xk, xv, H, B, T, beam, out, lo_off);
+        dec_cross_attn_kernel<<<H * B, 256, 0, s>>>(part, ks, bias, xk, xv, H, B, T, beam, out, lo_off, wmap);
         return;
     }
     const int W = B / beam;
@@ -1506,21 +1513,21 @@ void launch_dec_cross_attn(const float* part, int ks, const float* bias, const h
     if (beam > 1 && !valu_beam && ks <= 8) {
         static const bool kdirect = std::getenv("OSW_XATTN_KDIRECT") != nullptr;  // A/B switch
         if (kdirect) {
-            if (beam <= 5) dec_xattn_mfma_kernel<5, false><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st);
-            else dec_xattn_mfma_kernel<8, false><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st);
+            if (beam <= 5) dec_xattn_mfma_kernel<5, false><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap);
+            else dec_xattn_mfma_kernel<8, false><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap);
         } else {
-            if (beam <= 5) dec_xattn_mfma_kernel<5><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st);
-            else dec_xattn_mfma_kernel<8><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st);
+            if (beam <= 5) dec_xattn_mfma_kernel<5><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap);
+            else dec_xattn_mfma_kernel<8><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap);
         }
         return;
     }
     switch (beam) {
-        case 1: dec_xattn_chunk_kernel<1><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st); break;
-        case 2: dec_xattn_chunk_kernel<2><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st); break;
+        case 1: dec_xattn_chunk_kernel<1><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap); break;
+        case 2: dec_xattn_chunk_kernel<2><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap); break;
         case 3:
-        case 4: dec_xattn_chunk_kernel<4><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st); break;
-        case 5: dec_xattn_chunk_kernel<5><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st); break;
-        default: dec_xattn_chunk_kernel<8><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st); break;
+        case 4: dec_xattn_chunk_kernel<4><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap); break;
+        case 5: dec_xattn_chunk_kernel<5><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap); break;
+        default: dec_xattn_chunk_kernel<8><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap); break;
     }
 }
 

@@ -45,7 +45,7 @@ uint64_t hash_stream_key(uint64_t, int64_t);
 void launch_dec_self_attn(const float*, int, const float*, h16*, h16*, const int*, int, int, int, h16*, int64_t,
                           const int*, int, const SelState*, hipStream_t, int pos_row = 0);
 void launch_dec_cross_attn(const float*, int, const float*, const h16*, const h16*, int, int, int, int, h16*, int64_t,
-                           float*, int*, const SelState*, hipStream_t);
+                           float*, int*, const SelState*, hipStream_t, const int* wmap = nullptr);
 void launch_dec_resid_ln(const float*, int, int, int, const float*, float*, const float*, const float*, h16*, int64_t,
                          const h16*, const float*, const int*, const int*, int, int, hipStream_t, int pos_row = 0);
 void launch_dec_reduce_gelu(const float*, int, int, int, const float*, h16*, int64_t, hipStream_t);
@@ -303,6 +303,8 @@ struct osw_ctx {
     float* part2 = nullptr;    // second slab buffer of the fused small-batch step (<= PRO_ROWS rows)
     float* xws = nullptr;      // cross-attention per-chunk partials [R][H][XCHUNKS][XPART]
     int* xticket = nullptr;    // cross-attention arrival tickets [B][H] (zero between launches)
+    int* xmap_d = nullptr;     // osw_decode_window_list: [B] row group -> encoded window (a fixed address: graphs replay it)
+    const int* xmap = nullptr; // xmap_d while a list decode runs, else null (the identity)
     int* tail_ticket = nullptr; // split-K GEMM tails (ProArgs::tail_ticket)
     int* sel_arrive = nullptr; // select arrival counters: rows finalised + per-row slice tickets (zero between launches)
     int* budget = nullptr;     // per-row token budgets (osw_decode_opts::token_budget)
@@ -650,6 +652,7 @@ void setup_workspace(osw_ctx* c) {
     c->xws = dalloc<float>(R * d.n_text_head * XCHUNKS * XPART, o);
     c->xticket = dalloc<int>(B * d.n_text_head, o);
     HIPCHK(hipMemsetAsync(c->xticket, 0, (size_t)B * d.n_text_head * sizeof(int), c->stream));
+    c->xmap_d = dalloc<int>(B, o);
     c->budget = dalloc<int>(R, o);
     c->lp_hist = dalloc<float>(R * d.n_text_ctx, o);
     c->best_lp = dalloc<float>(B * d.n_text_ctx, o);
@@ -946,7 +949,7 @@ void decoder_step_fused(osw_ctx* c, int nb, int group, bool gather, const SelFus
             Timed t(c, CL_XATTN, 2.0 * nb * H * (double)T_ENC * 64 * 2);
             launch_dec_cross_attn(ps[last], ks, WF(c, p + ".xq.b"), c->XKV + (2 * l) * xkv_which,
                                   c->XKV + (2 * l + 1) * xkv_which, nb, H, T_ENC, group, c->dattn, lo_d, c->xws,
-                                  c->xticket, c->sel, c->stream);
+                                  c->xticket, c->sel, c->stream, c->xmap);
         }
         if (c->acap) align_capture(c, l, ps[last], ks, nb, xkv_which);
         plain(c->dattn, p + ".xo.w", D, D);
@@ -1044,7 +1047,7 @@ bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf 
             Timed t(c, CL_XATTN, 2.0 * nb * H * (double)T_ENC * 64 * 2);
             launch_dec_cross_attn(c->part, ks, WF(c, p + ".xq.b"), c->XKV + (2 * l) * xkv_which,
                                   c->XKV + (2 * l + 1) * xkv_which, nb, H, T_ENC, group, c->dattn, lo_d, c->xws,
-                                  c->xticket, c->sel, c->stream);
+                                  c->xticket, c->sel, c->stream, c->xmap);
         }
         if (c->acap) align_capture(c, l, c->part, ks, nb, xkv_which);
         ks = partial(c->dattn, D, p + ".xo.w", D, D);
@@ -1194,10 +1197,38 @@ HistRules hist_rules(const osw_decode_opts* o, const osw_dims& d) {
     return h;
 }
 
-void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r) {
-    REQUIRE(nb >= 1 && nb == c->n_encoded, "decode window count must equal the last encode call");
+// windows (osw_decode_window_list): decoder row group i attends encoded window windows[i]; the
+// cross-K/V planes keep the encode call's window count as their stride (c->xkv_windows, as in
+// sessions) and the cross-attention kernels read the K/V head offset through c->xmap.  Nothing
+// else knows: prompts, row state, tickets and results are those of a plain decode of nb windows.
+void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r, const int32_t* windows = nullptr) {
+    if (windows) {
+        REQUIRE(nb >= 1 && nb <= c->n_encoded, "window list: 1 <= n <= the last encode call's window count");
+        std::vector<char> seen((size_t)c->n_encoded, 0);
+        for (int i = 0; i < nb; ++i) {
+            REQUIRE(windows[i] >= 0 && windows[i] < c->n_encoded, "window list: index outside the last encode call");
+            REQUIRE(!seen[windows[i]], "window list: a window appears twice");
+            seen[windows[i]] = 1;
+        }
+    } else {
+        REQUIRE(nb >= 1 && nb == c->n_encoded, "decode window count must equal the last encode call");
+    }
     REQUIRE(o && r && r->tokens && r->n_tokens && r->sum_logprob && r->no_speech_prob && r->language,
             "null decode argument");
+    struct Mapped {  // the map and the plane stride hold for this call only
+        osw_ctx* c;
+        ~Mapped() {
+            c->xmap = nullptr;
+            c->xkv_windows = 0;
+        }
+    };
+    std::unique_ptr<Mapped> mapped;
+    if (windows) {
+        mapped.reset(new Mapped{c});
+        c->xkv_windows = c->n_encoded;
+        c->xmap = c->xmap_d;
+        HIPCHK(hipMemcpyAsync(c->xmap_d, windows, (size_t)nb * 4, hipMemcpyHostToDevice, c->stream));
+    }
     const osw_dims& d = c->d;
     const int V = d.n_vocab;
     const int n_pre = o->n_prefix;
@@ -1304,6 +1335,9 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r) 
                                     o->without_timestamps, o->max_initial_timestamp_index, beam, SP.num_hyp,
                                     SP.max_cand, lp_bits, group, it_bits, SP.budget ? 1 : 0, hr.penalty_bits(),
                                     hr.ngram, c->conf ? 1 : 0};
+        // a mapped decode bakes the map's address and the plane stride into its launches: its own
+        // key (a longer one, so no plain key equals it); the map's contents are data, not key
+        if (windows) key.push_back(c->n_encoded);
         c->dgraph = decode_graph(c, key, one_step, CH);
     }
     int steps = 0;
@@ -2729,6 +2763,19 @@ int osw_decode_windows(osw_ctx* c, int32_t n, const osw_decode_opts* opts, osw_w
     });
 }
 
+int osw_decode_window_list(osw_ctx* c, int32_t n, const int32_t* windows, const osw_decode_opts* opts,
+                           osw_window_result* res) {
+    return guard([&] {
+        REQUIRE(c && windows, "null argument");
+        std::lock_guard<std::mutex> lk(c->mu);
+        REQUIRE(!c->sess, "a decode session is open on this context (osw_session_end first)");
+        DeviceScope dev_scope_((c->device));
+        LaneCall call_(c);
+        decode(c, n, opts, res, windows);
+        resolve_events(c);
+    });
+}
+
 int osw_set_confidences(osw_ctx* c, int32_t enable) {
     return guard([&] {
         REQUIRE(c, "null ctx");
@@ -3156,24 +3203,44 @@ int osw_debug_enc_attn(osw_ctx* c, const void* qkv, int32_t nb, int32_t H, int32
     });
 }
 
-int osw_debug_dec_xattn(osw_ctx* c, const float* q_slabs, int32_t ks, const float* bias, const void* K, const void* V,
-                        int32_t rows, int32_t beam, int32_t legacy, float* out) {
+namespace {
+// one cross-attention launch on host data; window_map null: K / V hold one window per row group
+// (kv_windows == rows / beam), else row group w attends window window_map[w] of kv_windows
+int debug_dec_xattn(osw_ctx* c, const float* q_slabs, int32_t ks, const float* bias, const void* K, const void* V,
+                    int32_t kv_windows, const int32_t* window_map, int32_t rows, int32_t beam, int32_t legacy,
+                    float* out) {
     return guard([&] {
         REQUIRE(c && q_slabs && K && V && out, "null argument");
         REQUIRE(ks >= 1 && ks <= 32, "ks out of range");
         REQUIRE(beam >= 1 && beam <= MAX_BEAM && rows >= beam && rows % beam == 0, "rows must be windows x beam, beam <= 8");
         const int H = c->d.n_text_head, D = c->d.n_text_state, W = rows / beam;
         REQUIRE(W <= c->B, "more windows than the context's max_batch (its arrival tickets)");
+        if (window_map) {
+            REQUIRE(kv_windows >= 1 && kv_windows <= c->B && W <= kv_windows, "window map: 1 <= row groups <= kv_windows <= max_batch");
+            std::vector<char> seen((size_t)kv_windows, 0);
+            for (int i = 0; i < W; ++i) {
+                REQUIRE(window_map[i] >= 0 && window_map[i] < kv_windows, "window map: index outside K / V");
+                REQUIRE(!seen[window_map[i]], "window map: a window appears twice");
+                seen[window_map[i]] = 1;
+            }
+        } else {
+            REQUIRE(kv_windows == W, "K / V hold one window per row group");
+        }
         std::lock_guard<std::mutex> lk(c->mu);
         DeviceScope dev_scope_((c->device));
         GateLock gate_(capture_gate());
         TmpBufs tmp;
-        const size_t nq = (size_t)ks * rows * D, nkv = (size_t)W * H * T_ENC * 64, no = (size_t)rows * D;
+        const size_t nq = (size_t)ks * rows * D, nkv = (size_t)kv_windows * H * T_ENC * 64, no = (size_t)rows * D;
         float* dq = dalloc<float>(nq, tmp.v);
         float* db = dalloc<float>(D, tmp.v);
         h16* dk = dalloc<h16>(nkv, tmp.v);
         h16* dv = dalloc<h16>(nkv, tmp.v);
         h16* dout = dalloc<h16>(2 * no, tmp.v);  // hi, then lo
+        int* dmap = nullptr;
+        if (window_map) {
+            dmap = dalloc<int>((size_t)W, tmp.v);
+            HIPCHK(hipMemcpyAsync(dmap, window_map, (size_t)W * 4, hipMemcpyHostToDevice, c->stream));
+        }
         float* ws = legacy ? nullptr : dalloc<float>((size_t)rows * H * XCHUNKS * XPART, tmp.v);
         SelState* st = dalloc<SelState>((size_t)rows, tmp.v);
         HIPCHK(hipMemcpyAsync(dq, q_slabs, nq * 4, hipMemcpyHostToDevice, c->stream));
@@ -3185,7 +3252,7 @@ int osw_debug_dec_xattn(osw_ctx* c, const float* q_slabs, int32_t ks, const floa
         HIPCHK(hipMemsetAsync(dout, 0xff, 2 * no * 2, c->stream));
         HIPCHK(hipMemsetAsync(st, 0, (size_t)rows * sizeof(SelState), c->stream));
         launch_dec_cross_attn(dq, ks, (legacy && !bias) ? nullptr : db, dk, dv, rows, H, T_ENC, beam, dout, (int64_t)no, ws,
-                              c->xticket, st, c->stream);
+                              c->xticket, st, c->stream, dmap);
         hipError_t e = hipGetLastError();
         // the tickets are zero between launches (the last arriver resets its own); after a
         // failed launch they may not be, and the decode path shares them
@@ -3197,6 +3264,19 @@ int osw_debug_dec_xattn(osw_ctx* c, const float* q_slabs, int32_t ks, const floa
         HIPCHK(hipStreamSynchronize(c->stream));
         for (size_t i = 0; i < no; ++i) out[i] = (float)back[i] + (float)back[no + i];
     });
+}
+}  // namespace
+
+int osw_debug_dec_xattn(osw_ctx* c, const float* q_slabs, int32_t ks, const float* bias, const void* K, const void* V,
+                        int32_t rows, int32_t beam, int32_t legacy, float* out) {
+    return debug_dec_xattn(c, q_slabs, ks, bias, K, V, beam >= 1 ? rows / beam : 0, nullptr, rows, beam, legacy, out);
+}
+
+int osw_debug_dec_xattn_windows(osw_ctx* c, const float* q_slabs, int32_t ks, const float* bias, const void* K,
+                                const void* V, int32_t kv_windows, const int32_t* window_map, int32_t rows, int32_t beam,
+                                int32_t legacy, float* out) {
+    if (!window_map) return guard([&] { REQUIRE(false, "null window map"); });
+    return debug_dec_xattn(c, q_slabs, ks, bias, K, V, kv_windows, window_map, rows, beam, legacy, out);
 }
 
 int osw_debug_dec_self_attn(osw_ctx* c, const float* qkv_slabs, int32_t ks, const float* bias, void* kcache, void* vcache,

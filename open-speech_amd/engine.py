@@ -309,11 +309,25 @@ class WhisperEngine:
         return (probs, raw) if return_logits else probs
 
     def decode(self, n: int, cfg: DecodeConfig, prefix: list | None = None, dump_steps: int = 0,
-               languages: list | None = None) -> list[WindowOutput]:
+               languages: list | None = None, windows: list | None = None) -> list[WindowOutput]:
+        """Decode the ``n`` windows last encoded, or with ``windows`` (``n`` distinct indices into
+        the last encode call; osw_decode_window_list) just those: entry i of ``prefix``,
+        ``languages``, ``cfg.token_budget`` and of the result belongs to ``windows[i]``, and the
+        result is what encoding only those windows in that order and decoding them gives, bit for
+        bit.  The encoded windows stay as they are for later ``decode`` / ``align`` calls."""
         o, keep = self._opts(cfg, n, prefix, languages)
         r, bufs, dump = self._result(n, dump_steps)
         self._set_confidences(cfg.confidences)
-        _lib.check(self.lib.osw_decode_windows(self.ctx, n, C.byref(o), C.byref(r)), "osw_decode_windows")
+        if windows is None:
+            _lib.check(self.lib.osw_decode_windows(self.ctx, n, C.byref(o), C.byref(r)), "osw_decode_windows")
+        else:
+            if len(windows) != n:
+                raise ValueError("one window index per decoded window")
+            idx = np.ascontiguousarray([int(w) for w in windows], dtype=np.int32).reshape(-1)
+            if not n:
+                idx = np.zeros(1, np.int32)
+            _lib.check(self.lib.osw_decode_window_list(self.ctx, n, _i32p(idx), C.byref(o), C.byref(r)),
+                       "osw_decode_window_list")
         del keep
         return self._outputs(n, bufs, dump, cfg.confidences)
 
@@ -558,6 +572,34 @@ class WhisperEngine:
                                                 K.ctypes.data_as(C.c_void_p), V.ctypes.data_as(C.c_void_p), rows,
                                                 int(beam), int(bool(legacy)), out.ctypes.data_as(fp)),
                    "osw_debug_dec_xattn")
+        return out
+
+    def debug_dec_xattn_windows(self, q_slabs: np.ndarray, bias, K: np.ndarray, V: np.ndarray, window_map,
+                                beam: int = 1, legacy: bool = False) -> np.ndarray:
+        """``debug_dec_xattn`` with a window map (osw_debug_dec_xattn_windows): K and V fp16
+        [kv_windows][H][1500][64], q_slabs fp32 [ks][len(window_map) * beam][D]; row group w
+        attends window ``window_map[w]``."""
+        q = np.ascontiguousarray(q_slabs, dtype=np.float32)
+        K = np.ascontiguousarray(K, dtype=np.float16)
+        V = np.ascontiguousarray(V, dtype=np.float16)
+        wm = np.ascontiguousarray([int(w) for w in window_map], dtype=np.int32).reshape(-1)
+        ks, rows, Dm = q.shape
+        KW, H = K.shape[:2]
+        if K.shape != (KW, H, 1500, 64) or V.shape != K.shape or Dm != self.dims.n_text_state or \
+                H != self.dims.n_text_head or rows != len(wm) * beam:
+            raise ValueError("shapes: q [ks][len(window_map)*beam][D], K/V [kv_windows][H][1500][64] with the "
+                             "engine's H and D")
+        b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+        if b is not None and b.shape != (Dm,):
+            raise ValueError("bias must be [D]")
+        out = np.empty((rows, Dm), np.float32)
+        fp = C.POINTER(C.c_float)
+        mp = _i32p(wm if len(wm) else np.zeros(1, np.int32))
+        _lib.check(self.lib.osw_debug_dec_xattn_windows(self.ctx, q.ctypes.data_as(fp), ks,
+                                                        None if b is None else b.ctypes.data_as(fp),
+                                                        K.ctypes.data_as(C.c_void_p), V.ctypes.data_as(C.c_void_p),
+                                                        KW, mp, rows, int(beam), int(bool(legacy)),
+                                                        out.ctypes.data_as(fp)), "osw_debug_dec_xattn_windows")
         return out
 
     def debug_dec_self_attn(self, qkv_slabs: np.ndarray, bias: np.ndarray, kcache: np.ndarray, vcache: np.ndarray,

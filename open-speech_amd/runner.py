@@ -205,7 +205,8 @@ class _SessionLane(_Worker):
     the batch's longest window.  A session holds one decode configuration
     (``TranscribeOptions.key()``): a lane admits only requests of its session's key, and
     opens a session for another key once its own has drained.  Requests a session cannot
-    hold (segments.session_supported: temperature > 0, max_new_tokens, beam_size > 5)
+    hold (segments.session_supported: temperature > 0 or a fallback ladder, max_new_tokens,
+    beam_size > 5)
     run through the batched seek loop of an idle lane.
     """
 

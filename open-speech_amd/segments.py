@@ -25,10 +25,33 @@ after a window's decode its text tokens are aligned on the GPU (``engine.align``
 into words, clamped and attached to the window's segments, and the seek rule gains
   not single_timestamp_ending and last_word_end > time_offset -> seek = round(last_word_end * 100)
 with ``last_speech_timestamp`` carried from window to window.
+
+Temperature fallback (``TranscribeOptions.temperature`` a sequence, e.g. faster-whisper's default
+ladder (0.0, 0.2, 0.4, 0.6, 0.8, 1.0); faster-whisper ``generate_with_fallback``, restated from
+the upstream code, not pinned).  Every window of a chunk is decoded at temperatures[0] as above;
+then, per window and for each temperature T_k in order:
+  decode (beam or greedy at T_k == 0, else ``best_of`` sampled rows), avg_logprob, text, ratio
+  needs_fallback = compression_ratio > compression_ratio_threshold   (else: "below the ratio")
+  needs_fallback |= avg_logprob < log_prob_threshold
+  needs_fallback = False if no_speech_prob > no_speech_threshold and avg_logprob < log_prob_threshold
+  (a threshold that is None switches its own test off); stop at the first T_k that needs none
+  every T_k failed: keep the highest avg_logprob among the below-the-ratio results (among all
+  when there are none; the first on ties) and report the last temperature as the window's
+The windows of a chunk that still need a retry are decoded together at the next temperature with
+``engine.decode(..., windows=[their indices in the chunk])`` (osw_decode_window_list: only they
+are decoded, from the cross-K/V the chunk's one encoder call left; nothing is encoded or detected
+again: the language tokens are attempt 0's).  ``Segment.temperature`` and the
+``prompt_reset_on_temperature`` test use the window's own final temperature; the silence skip,
+the segment split, the confidences and the word alignment run once, on the kept result.
+Seeds: attempt k of chunk call number ``calls`` (which advances once per chunk) samples with
+  (opts.seed + 0x9E3779B1 * calls + 0x85EBCA6B * k) mod 2**64
+so k = 0 is the scalar-temperature seed.  The chunk size uses the largest row group (beam_size or
+best_of) of any attempt.
 """
 from __future__ import annotations
 
 import itertools
+import math
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -53,7 +76,9 @@ class TranscribeOptions:
     suppress_tokens: tuple = (-1,)
     without_timestamps: bool = False
     max_initial_timestamp: float = 1.0
-    temperature: float = 0.0
+    # a float, or a sequence of floats: faster-whisper's fallback ladder (module docstring); kept
+    # as a float when it has one entry, else as a tuple
+    temperature: float | tuple = 0.0
     beam_size: int = 5             # faster-whisper / reference default (src/backends/faster_whisper.py:237)
     patience: float = 1.0
     length_penalty: float = 1.0
@@ -82,12 +107,36 @@ class TranscribeOptions:
     detect_only: bool = False
 
     def __post_init__(self):
+        t = self.temperature
+        if isinstance(t, (str, bytes)):
+            raise ValueError(f"temperature must be a number or a sequence of numbers, got {t!r}")
+        try:
+            ladder = tuple(float(x) for x in t) if hasattr(t, "__iter__") else (float(t),)
+        except (TypeError, ValueError):
+            raise ValueError(f"temperature must be a number or a sequence of numbers, got {t!r}") from None
+        if not ladder:
+            raise ValueError("temperature: an empty sequence")
+        if not all(math.isfinite(x) and x >= 0 for x in ladder):
+            raise ValueError(f"temperature entries must be finite and >= 0, got {t!r}")
+        if hasattr(t, "__iter__"):
+            self.temperature = ladder[0] if len(ladder) == 1 else ladder
         if not float(self.repetition_penalty) > 0:
             raise ValueError(f"repetition_penalty must be > 0, got {self.repetition_penalty!r}")
         if int(self.no_repeat_ngram_size) < 0:
             raise ValueError(f"no_repeat_ngram_size must be >= 0, got {self.no_repeat_ngram_size!r}")
 
+    @property
+    def temperatures(self) -> tuple:
+        t = self.temperature
+        return tuple(t) if isinstance(t, tuple) else (t,)
+
     def key(self):
+        # the fallback thresholds join only when they differ from the defaults, so the key of
+        # every earlier configuration stays what it was
+        th = (self.compression_ratio_threshold, self.log_prob_threshold, self.no_speech_threshold)
+        return self._key() + (() if th == (2.4, -1.0, 0.6) else (th,))
+
+    def _key(self):
         return (self.task, self.language, self.initial_prompt, self.condition_on_previous_text,
                 self.without_timestamps, tuple(self.suppress_tokens), self.suppress_blank, self.beam_size,
                 self.patience, self.length_penalty, self.temperature, self.best_of, self.tokens_per_second,
@@ -205,9 +254,12 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
             s.result.language_probability = 1.0
         states.append(s)
     max_init = int(round(opts.max_initial_timestamp / TIME_PRECISION))
-    sampling = opts.temperature > 0
-    beam = 1 if sampling else max(1, int(opts.beam_size))
-    group = max(1, int(opts.best_of)) if sampling else beam  # decoder rows per window
+    temps = opts.temperatures
+
+    def rows_per_window(t):  # decoder rows per window: best_of samples, or the beam
+        return max(1, int(opts.best_of)) if t > 0 else max(1, int(opts.beam_size))
+
+    group = max(rows_per_window(t) for t in temps)  # the largest of any attempt
     B = max(1, min(engine.max_batch, getattr(engine, "max_rows", engine.max_batch) // group))
     calls = 0
     while True:
@@ -236,28 +288,38 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
                         raise ValueError(f"the prompt is {max_length - int(opts.max_new_tokens)} tokens and "
                                          f"max_new_tokens is {opts.max_new_tokens}: their sum exceeds the "
                                          "model's maximum length (448)")
-                cfg = DecodeConfig(max_length=max_length, task=opts.task, language_token=None, suppress_tokens=suppress,
-                                   suppress_blank=opts.suppress_blank, without_timestamps=opts.without_timestamps,
-                                   max_initial_timestamp_index=max_init, beam_size=beam, patience=opts.patience,
-                                   length_penalty=opts.length_penalty, temperature=opts.temperature,
-                                   best_of=opts.best_of, seed=(opts.seed + 0x9E3779B1 * calls) & (2**64 - 1),
-                                   repetition_penalty=float(opts.repetition_penalty),
-                                   no_repeat_ngram_size=int(opts.no_repeat_ngram_size),
-                                   confidences=bool(opts.token_logprobs))
-                if opts.tokens_per_second:
-                    cfg.token_budget = tuple(int(np.ceil(opts.tokens_per_second * z * FRAME_SEC)) + 2
-                                             for _, _, z in wins)
+                budgets = tuple(int(np.ceil(opts.tokens_per_second * z * FRAME_SEC)) + 2
+                                for _, _, z in wins) if opts.tokens_per_second else None
+
+                def attempt_cfg(k, which=None, max_length=max_length, calls=calls, budgets=budgets):
+                    # attempt k of this chunk, for the windows `which` of it (None: all of them)
+                    t = temps[k]
+                    return DecodeConfig(
+                        max_length=max_length, task=opts.task, language_token=None, suppress_tokens=suppress,
+                        suppress_blank=opts.suppress_blank, without_timestamps=opts.without_timestamps,
+                        max_initial_timestamp_index=max_init, beam_size=1 if t > 0 else max(1, int(opts.beam_size)),
+                        patience=opts.patience, length_penalty=opts.length_penalty, temperature=t,
+                        best_of=opts.best_of,
+                        seed=(opts.seed + 0x9E3779B1 * calls + 0x85EBCA6B * k) & (2**64 - 1),
+                        repetition_penalty=float(opts.repetition_penalty),
+                        no_repeat_ngram_size=int(opts.no_repeat_ngram_size), confidences=bool(opts.token_logprobs),
+                        token_budget=None if budgets is None else
+                        (budgets if which is None else tuple(budgets[i] for i in which)))
+
                 calls += 1
                 prefixes = [p for _, p in chunk] if _plen else None
-                outs = engine.decode(len(chunk), cfg, prefix=prefixes, languages=langs)
+                outs = engine.decode(len(chunk), attempt_cfg(0), prefix=prefixes, languages=langs)
+                win_temps = [temps[0]] * len(chunk)
+                if len(temps) > 1:
+                    outs, win_temps = _fallback(engine, chunk, outs, prefixes, attempt_cfg, temps, opts, tok)
                 if not opts.word_timestamps:
-                    for (s, _), w, out in zip(chunk, wins, outs):
-                        _consume(s, w, out, opts, tok)
+                    for (s, _), w, out, t in zip(chunk, wins, outs, win_temps):
+                        _consume(s, w, out, opts, tok, t)
                     continue
                 # word timestamps: one alignment call for the chunk's windows while their
                 # cross-K/V is still resident, then the segments with their words
                 from .engine import AlignWindow
-                plans = [_plan(s, w, out, opts, tok) for (s, _), w, out in zip(chunk, wins, outs)]
+                plans = [_plan(s, w, out, opts, tok, t) for (s, _), w, out, t in zip(chunk, wins, outs, win_temps)]
                 req = [(i, p) for i, p in enumerate(plans) if p is not None and p["text_tokens"]]
                 # the forced sequence adds 5 positions: a window that decoded more text tokens than
                 # fit (a model that never emits <|endoftext|>) aligns the ones that do
@@ -273,6 +335,63 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
         code = tok.language_code(s.lang_token) if s.lang_token is not None else (opts.language or "en")
         s.result.language = code
     return [s.result for s in states]
+
+
+def needs_fallback(out, avg_logprob: float, cr: float, opts: TranscribeOptions):
+    """faster-whisper ``generate_with_fallback``'s tests on one decode result: (needs a retry at
+    the next temperature, is below the compression-ratio threshold)."""
+    needs, below = False, False
+    if opts.compression_ratio_threshold is not None:
+        if cr > opts.compression_ratio_threshold:
+            needs = True
+        else:
+            below = True
+    if opts.log_prob_threshold is not None and avg_logprob < opts.log_prob_threshold:
+        needs = True
+    if (opts.no_speech_threshold is not None and out.no_speech_prob > opts.no_speech_threshold
+            and opts.log_prob_threshold is not None and avg_logprob < opts.log_prob_threshold):
+        needs = False  # silence
+    return needs, below
+
+
+def _fallback(engine, chunk: list, outs0: list, prefixes, attempt_cfg, temps: tuple, opts: TranscribeOptions,
+              tok: WhisperTokenizer):
+    """The retries of one chunk after its attempt 0 (module docstring): the kept result and the
+    final temperature of every window.  A clip whose language attempt 0 detected keeps it (and
+    that window's language probabilities): the retries name it."""
+    n = len(chunk)
+    for (s, _), out in zip(chunk, outs0):
+        if s.lang_token is None:
+            s.lang_token = out.language
+            _set_language_probs(s.result, getattr(out, "language_probs", None), out.language, tok)
+    tried = [[] for _ in range(n)]   # per window: (avg_logprob, below the ratio, result) of every attempt
+    final = [temps[0]] * n
+    kept = list(outs0)
+    failing = []
+    for k in range(len(temps)):
+        if k == 0:
+            which, outs = list(range(n)), outs0
+        else:
+            which = failing
+            outs = engine.decode(len(which), attempt_cfg(k, which),
+                                 prefix=[prefixes[i] for i in which] if prefixes else None,
+                                 languages=[chunk[i][0].lang_token for i in which], windows=list(which))
+        failing = []
+        for i, out in zip(which, outs):
+            avg = out.sum_logprob / (len(out.tokens) + 1)
+            needs, below = needs_fallback(out, avg, compression_ratio(tok.decode(out.tokens).strip()), opts)
+            tried[i].append((avg, below, out))
+            final[i] = temps[k]
+            if needs:
+                failing.append(i)
+            else:
+                kept[i] = out
+        if not failing:
+            break
+    for i in failing:  # every temperature failed
+        pool = [r for r in tried[i] if r[1]] or tried[i]
+        kept[i] = max(pool, key=lambda r: r[0])[2]
+    return kept, final
 
 
 def _set_language_probs(res: ClipResult, probs, lang_token: int, tok: WhisperTokenizer) -> None:
@@ -309,13 +428,14 @@ def _detect_clips(engine, pcm_list: list, nf: list, tok: WhisperTokenizer) -> li
 
 def session_supported(opts: TranscribeOptions) -> bool:
     """Decode sessions (osw_session_*) hold one decode configuration for every window:
-    temperature 0, beam_size <= 5, and no max_new_tokens (whose max_length depends on
-    each window's prompt length)."""
+    temperature 0 (one entry: no fallback ladder), beam_size <= 5, and no max_new_tokens
+    (whose max_length depends on each window's prompt length)."""
     if opts.word_timestamps:   # the alignment pass needs the window's cross-K/V of a batched decode call
         return False
     if opts.detect_only:       # one decoder step per clip, no seek loop
         return False
-    return not (opts.temperature > 0) and opts.max_new_tokens is None and 1 <= int(opts.beam_size) <= 5
+    temps = opts.temperatures   # (a fallback ladder takes the batched seek loop: its retries are decode calls)
+    return len(temps) == 1 and not (temps[0] > 0) and opts.max_new_tokens is None and 1 <= int(opts.beam_size) <= 5
 
 
 def session_config(opts: TranscribeOptions, suppress: tuple) -> DecodeConfig:
@@ -361,15 +481,16 @@ def finish_clip(s: _ClipState, opts: TranscribeOptions, tok: WhisperTokenizer) -
     return s.result
 
 
-def _consume(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperTokenizer) -> None:
-    plan = _plan(s, win, out, opts, tok)
+def _consume(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperTokenizer, temperature=None) -> None:
+    plan = _plan(s, win, out, opts, tok, temperature)
     if plan is not None:
         _apply(s, win, out, opts, tok, plan, None)
 
 
-def _plan(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperTokenizer):
+def _plan(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperTokenizer, temperature=None):
     """The window's segments before they are kept (None: the window was skipped as silence),
-    with the text tokens word timing aligns."""
+    with the text tokens word timing aligns.  ``temperature``: the window's own final one
+    (None: the options' scalar)."""
     st = tok.special
     _, seek, segment_size = win
     if s.lang_token is None:
@@ -393,13 +514,15 @@ def _plan(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperTokenize
                                                                  segment_size * FRAME_SEC, seek, lps)
     text_tokens = [int(t) for sg in segs for t in sg["tokens"] if t < st.eot]
     return dict(segs=segs, new_seek=new_seek, single_ending=single_ending, avg_logprob=avg_logprob, cr=cr,
-                text_tokens=text_tokens, time_offset=time_offset)
+                text_tokens=text_tokens, time_offset=time_offset,
+                temperature=opts.temperatures[0] if temperature is None else temperature)
 
 
 def _apply(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperTokenizer, plan: dict, alignment) -> None:
     """Keep the planned segments (with their words when ``alignment`` is given) and move the seek."""
     _, seek, segment_size = win
     segs, new_seek, avg_logprob, cr = plan["segs"], plan["new_seek"], plan["avg_logprob"], plan["cr"]
+    temperature = plan["temperature"]
     if opts.word_timestamps:
         lang = tok.language_code(s.lang_token) if s.lang_token is not None else opts.language
         s.last_speech_timestamp = add_word_timestamps(segs, tok, alignment, lang, opts.prepend_punctuations,
@@ -416,13 +539,13 @@ def _apply(s: _ClipState, win, out, opts: TranscribeOptions, tok: WhisperTokeniz
             continue
         s.all_tokens.extend(t)
         s.result.segments.append(Segment(id=len(s.result.segments), seek=seek, start=sg["start"], end=sg["end"],
-                                         text=txt, tokens=list(t), temperature=opts.temperature,
+                                         text=txt, tokens=list(t), temperature=temperature,
                                          avg_logprob=avg_logprob, compression_ratio=cr,
                                          no_speech_prob=out.no_speech_prob,
                                          words=[Word(**w) for w in sg["words"]] if "words" in sg else None,
                                          token_logprobs=list(sg["token_logprobs"]) if "token_logprobs" in sg
                                          else None))
-    if not opts.condition_on_previous_text or opts.temperature > opts.prompt_reset_on_temperature:
+    if not opts.condition_on_previous_text or temperature > opts.prompt_reset_on_temperature:
         s.prompt_reset_since = len(s.all_tokens)
     s.seek = new_seek
     s.done = s.seek >= s.content_frames
