@@ -60,6 +60,13 @@
  *                 window that failed its compression-ratio or log-probability test is generated
  *                 again at the next temperature from the encoder output it already has; the
  *                 reference passes one scalar temperature (src/backends/faster_whisper.py:238)
+ *   osw_decode_opts::task_token < 0, osw_align_window::language < 0 && task < 0
+ *       replace   WhisperModel(model_id) for the English-only checkpoints of the reference's
+ *                 registry (src/model_registry.py:7-21: tiny.en, base.en, small.en, medium.en,
+ *                 faster-distil-whisper-small.en / -medium.en, n_vocab 51864): faster-whisper's
+ *                 Tokenizer(multilingual=False) [upstream], whose sot_sequence is
+ *                 (<|startoftranscript|>,) with no language and no task token, in generate,
+ *                 detect_language (answered "en" by the caller) and find_alignment
  *
  * Conventions: every call returns 0 (OSW_OK) or a negative code; the message of
  * the last failure on the calling thread is osw_last_error().  Host buffers are
@@ -119,7 +126,14 @@ typedef struct osw_window {
 } osw_window;
 
 typedef struct osw_decode_opts {
-    int32_t task_token;          /* <|transcribe|> or <|translate|> */
+    /* <|transcribe|> or <|translate|>.  < 0: an English-only model, whose start sequence is
+     * <|startoftranscript|> alone: every prompt is [prefix..., sot(, no_timestamps)];
+     * language_token, language_tokens, first_lang, n_langs and osw_session_window::language_token
+     * are ignored, osw_window_result::language comes back -1, osw_detect_language returns
+     * OSW_EINVAL and osw_get_language_probs OSW_ESTATE.  With timestamps <|startoftranscript|>
+     * is the last prompt position, so that one decoder step gives both no_speech_prob (softmax
+     * of its raw logits) and the first sampled token (the same logits under the rules). */
+    int32_t task_token;
     int32_t language_token;      /* -1: detect from the <|startoftranscript|> logits */
     int32_t suppress_blank;      /* suppress " " and <|endoftext|> at the first sampled step */
     int32_t without_timestamps;  /* 0: timestamp rules on (faster-whisper default) */
@@ -347,7 +361,8 @@ int osw_set_confidences(osw_ctx* ctx, int32_t enable);
 int osw_get_token_logprobs(osw_ctx* ctx, int32_t i, float* cum, int32_t cap, int32_t* n);
 /* probs[n_langs] of the same result i: softmax over logits[first_lang .. first_lang + n_langs) at
  * the <|startoftranscript|> step (CTranslate2 detect_language's distribution), whether the
- * language was detected or given.  n_langs must be the decode call's.  OSW_ESTATE as above. */
+ * language was detected or given.  n_langs must be the decode call's.  OSW_ESTATE as above, and
+ * after an English-only decode (task_token < 0), which records no language distribution. */
 int osw_get_language_probs(osw_ctx* ctx, int32_t i, float* probs, int32_t n_langs);
 /* Language detection alone for the n windows of the last osw_encode_windows call: one decoder
  * step on <|startoftranscript|> (no prefix), then the same language softmax; probs [n][n_langs],
@@ -355,7 +370,8 @@ int osw_get_language_probs(osw_ctx* ctx, int32_t i, float* probs, int32_t n_lang
  * only (sot, task_token, first_lang, n_langs).  Needs no osw_set_confidences, touches no result
  * of an earlier call, and a later osw_decode_windows of the same windows returns what it would
  * have without it.  Runs on the context's stream and allocates nothing.  Replaces
- * WhisperModel.detect_language() -> ctranslate2 Whisper.detect_language [upstream].  OSW_EINVAL
+ * WhisperModel.detect_language() -> ctranslate2 Whisper.detect_language [upstream].  An
+ * English-only model (opts->task_token < 0) has nothing to detect: OSW_EINVAL before any launch.  OSW_EINVAL
  * while a session is open. */
 int osw_detect_language(osw_ctx* ctx, int32_t n, const osw_decode_opts* opts, float* probs, float* raw_logits);
 
@@ -367,7 +383,10 @@ int osw_detect_language(osw_ctx* ctx, int32_t n, const osw_decode_opts* opts, fl
 int osw_set_alignment_heads(osw_ctx* ctx, const int32_t* layer_head_pairs, int32_t n);
 
 /* One window to align: the forced sequence is [sot, language, task, no_timestamps,
- * tokens[0 .. n_tokens), eot] (no previous-text prefix; every text token < eot). */
+ * tokens[0 .. n_tokens), eot] (no previous-text prefix; every text token < eot).  language < 0
+ * and task < 0 together: an English-only model's [sot, no_timestamps, tokens..., eot]
+ * (faster-whisper passes the tokenizer's sot_sequence, (sot,) for such a model); the rows kept
+ * are [no_timestamps, tokens...] either way.  One of the two negative alone: OSW_EINVAL. */
 typedef struct osw_align_window {
     int32_t window;               /* index into the last encode / decode / transcribe_batch call */
     int32_t sot, language, task, no_timestamps, eot;
@@ -390,7 +409,8 @@ typedef struct osw_align_result {
  * (transformers' _dynamic_time_warping tie rule) and the first frame of each token.  A
  * window's result does not depend on the others of the call.  Replaces ctranslate2
  * Whisper.align as faster-whisper's find_alignment calls it [upstream].  OSW_EINVAL while a
- * session is open, for a window index the last call does not hold, or n_tokens + 5 > n_text_ctx. */
+ * session is open, for a window index the last call does not hold, or n_tokens + 5 > n_text_ctx
+ * (English-only: n_tokens + 3). */
 int osw_align_windows(osw_ctx* ctx, int32_t n, const osw_align_window* w, osw_align_result* res);
 /* M [T = n_tokens + 1][F] of `window` as the last osw_align_windows call left it (*T = *F = 0
  * when that call did not align it or it had no text); out may be NULL to query the shape. */

@@ -194,7 +194,9 @@ def load() -> C.CDLL:
         return lib
 
 
+OSW_EINVAL = -22
 OSW_EHIP = -100
+OSW_ESTATE = -101
 OSW_ECAPTURE = -102
 
 

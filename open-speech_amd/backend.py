@@ -287,7 +287,19 @@ class HipWhisperBackend:
         if no_repeat_ngram_size is None:
             no_repeat_ngram_size = int(os.environ.get("STT_HIP_NO_REPEAT_NGRAM_SIZE", "0"))
         pcm = decode_audio_bytes(audio)
-        opts = TranscribeOptions(task=task, language=language if (language and task == "transcribe") else None,
+        run_task = task
+        if not m.tokenizer.special.multilingual:
+            # faster-whisper with a model that is not multilingual: any language becomes "en" and
+            # the tokenizer drops the task, so translate decodes as transcription
+            coerced = []
+            if language and language != "en":
+                coerced.append(f"language {language!r} replaced by 'en'")
+            if task != "transcribe":
+                coerced.append(f"task {task!r} decoded as transcription")
+            if coerced:
+                logger.warning("Model %s is English-only: %s", model_id, "; ".join(coerced))
+            language, run_task = None, "transcribe"
+        opts = TranscribeOptions(task=run_task, language=language if (language and task == "transcribe") else None,
                                  initial_prompt=prompt or None, temperature=fallback_temperatures(temperature),
                                  compression_ratio_threshold=2.4 if compression_ratio_threshold is None
                                  else float(compression_ratio_threshold),

@@ -30,16 +30,17 @@ void launch_align_scores(const float* part, int ks, const float* bias, const h16
 // the forced pass's self-attention in fp32 (kc / vc: this layer's fp32 cache, [rows][H][ctx][64])
 void launch_align_self_attn(const float* part, int ks, const float* bias, float* kc, float* vc, const int* pos, int B,
                             int H, int ctx, h16* out, int64_t lo_off, const SelState* st, hipStream_t s);
-// log token_prob of the forced token predicted at this position (positions 3 .. len - 3), the
-// next forced token into cur_tok, and the row's done flag once its sequence ends
+// log token_prob of the forced token predicted at this position (positions head .. len - 3,
+// head[row] = <|notimestamps|>'s position: 3, or 1 in an English-only model's forced sequence),
+// the next forced token into cur_tok, and the row's done flag once its sequence ends
 void launch_align_tail(const float* logits, int rows, int V, int eot, int ctx, const int* pos, const int* slot,
-                       const int* len, const int* forced, float* token_logprob, int* cur_tok, SelState* st,
-                       hipStream_t s);
+                       const int* len, const int* head, const int* forced, float* token_logprob, int* cur_tok,
+                       SelState* st, hipStream_t s);
 void launch_align_bump(int* pos, hipStream_t s);
-// scores -> M [slot][T = len - 4][1500-float rows, F used]; stats: 2 floats per (slot, head, position),
-// colstats: 2 floats per (slot, head, frame)
+// scores -> M [slot][T = len - slot_head - 1][1500-float rows, F used]; stats: 2 floats per (slot, head,
+// position), colstats: 2 floats per (slot, head, frame)
 void launch_align_post(const float* scores, int n_slots, int n_heads, int pstride, const int* slot_len,
-                       const int* slot_frames, const int* slot_width, float* stats, float* colstats, float* M,
+                       const int* slot_head, const int* slot_frames, const int* slot_width, float* stats, float* colstats, float* M,
                        hipStream_t s);
 // DTW over x (neg: over -x) of slot i: x + i * xstride, rows of ldx floats, T[i] x F[i] cells.
 // trace: (T + 1)(F + 1) bytes per slot at i * tstride; path: [slot][2][pcap] ints, filled from

@@ -134,13 +134,15 @@ __global__ __launch_bounds__(256) void align_self_attn_kernel(const float* __res
 // token, then the row's next forced token (or its done flag)
 __global__ __launch_bounds__(256) void align_tail_kernel(const float* __restrict__ logits, int V, int eot, int ctx,
                                                          const int* __restrict__ pos, const int* __restrict__ slot,
-                                                         const int* __restrict__ len, const int* __restrict__ forced,
+                                                         const int* __restrict__ len, const int* __restrict__ head,
+                                                         const int* __restrict__ forced,
                                                          float* __restrict__ token_logprob, int* __restrict__ cur_tok,
                                                          SelState* __restrict__ st) {
     __shared__ float red[4];
     const int b = blockIdx.x, sl = slot[b], p = pos[0], L = len[b];
     if (sl < 0 || p >= L) return;
-    if (p >= 3 && p <= L - 3) {
+    const int hd = head[b];  // <|notimestamps|>'s position: 3, English-only 1
+    if (p >= hd && p <= L - 3) {
         const float* lg = logits + (int64_t)b * V;
         const int tok = forced[(int64_t)b * ctx + p + 1];
         float m = -INFINITY;
@@ -150,7 +152,7 @@ __global__ __launch_bounds__(256) void align_tail_kernel(const float* __restrict
         for (int i = threadIdx.x; i < eot; i += 256) s += expf(lg[i] - m);
         s = block_sum(s, red);
         // the log-probability: a forced token may be far too unlikely for an fp32 probability
-        if (threadIdx.x == 0) token_logprob[(int64_t)sl * ctx + p - 3] = (lg[tok] - m) - logf(s);
+        if (threadIdx.x == 0) token_logprob[(int64_t)sl * ctx + p - hd] = (lg[tok] - m) - logf(s);
     }
     if (threadIdx.x == 0) {
         if (p + 1 < L) cur_tok[b] = forced[(int64_t)b * ctx + p + 1];
@@ -247,20 +249,21 @@ __device__ __forceinline__ float align_median(const float* __restrict__ scores, 
 }
 
 // grid (frame blocks, T rows, slots): M[t][f] = mean over heads (list order) of the median-
-// filtered normalised weight of forced position t + 3
+// filtered normalised weight of forced position t + slot_head (<|notimestamps|>'s position)
 __global__ __launch_bounds__(256) void align_matrix_kernel(const float* __restrict__ scores,
                                                            const float* __restrict__ stats,
                                                            const float* __restrict__ colstats, int n_heads,
                                                            int pstride, const int* __restrict__ slot_len,
+                                                           const int* __restrict__ slot_head,
                                                            const int* __restrict__ slot_frames,
                                                            const int* __restrict__ slot_width, float* __restrict__ M) {
     const int f = blockIdx.x * 256 + threadIdx.x, t = blockIdx.y, sl = blockIdx.z;
-    const int P = slot_len[sl], F = slot_frames[sl], W = slot_width[sl];
-    if (t >= P - 4 || f >= F) return;
+    const int P = slot_len[sl], F = slot_frames[sl], W = slot_width[sl], hd = slot_head[sl];
+    if (t >= P - hd - 1 || f >= F) return;
     const bool filter = F > W / 2;  // transformers' _median_filter leaves shorter inputs unchanged
     float acc = 0.f;
     for (int hi = 0; hi < n_heads; ++hi) {
-        const int64_t sh = (int64_t)sl * n_heads + hi, row = sh * pstride + t + 3;
+        const int64_t sh = (int64_t)sl * n_heads + hi, row = sh * pstride + t + hd;
         const float* cs = colstats + 2 * sh * T_KEYS;
         float v;
         if (!filter) v = (align_prob(scores, stats, row, f) - cs[2 * f]) / cs[2 * f + 1];
@@ -367,22 +370,23 @@ void launch_align_self_attn(const float* part, int ks, const float* bias, float*
 }
 
 void launch_align_tail(const float* logits, int rows, int V, int eot, int ctx, const int* pos, const int* slot,
-                       const int* len, const int* forced, float* token_logprob, int* cur_tok, SelState* st,
-                       hipStream_t s) {
-    align_tail_kernel<<<rows, 256, 0, s>>>(logits, V, eot, ctx, pos, slot, len, forced, token_logprob, cur_tok, st);
+                       const int* len, const int* head, const int* forced, float* token_logprob, int* cur_tok,
+                       SelState* st, hipStream_t s) {
+    align_tail_kernel<<<rows, 256, 0, s>>>(logits, V, eot, ctx, pos, slot, len, head, forced, token_logprob, cur_tok,
+                                           st);
 }
 
 void launch_align_bump(int* pos, hipStream_t s) { align_bump_kernel<<<1, 1, 0, s>>>(pos); }
 
 void launch_align_post(const float* scores, int n_slots, int n_heads, int pstride, const int* slot_len,
-                       const int* slot_frames, const int* slot_width, float* stats, float* colstats, float* M,
+                       const int* slot_head, const int* slot_frames, const int* slot_width, float* stats, float* colstats, float* M,
                        hipStream_t s) {
     const int fb = (T_KEYS + 255) / 256;
     align_softmax_stats_kernel<<<n_slots * n_heads * pstride, 256, 0, s>>>(scores, n_heads, pstride, slot_len, stats);
     align_colstats_kernel<<<dim3(fb, n_heads, n_slots), 256, 0, s>>>(scores, stats, n_heads, pstride, slot_len,
                                                                       slot_frames, colstats);
     align_matrix_kernel<<<dim3(fb, pstride, n_slots), 256, 0, s>>>(scores, stats, colstats, n_heads, pstride, slot_len,
-                                                                    slot_frames, slot_width, M);
+                                                                    slot_head, slot_frames, slot_width, M);
 }
 
 void launch_align_dtw(const float* x, int64_t xstride, int ldx, int neg, int n_slots, const int* T, const int* F,

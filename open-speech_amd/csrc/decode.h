@@ -20,7 +20,10 @@ struct SelParams {
     int lang_pos;          // prompt position holding the language token (-1 placeholder => detect)
     int max_length;
     int pstride;           // ints per row of the prompt buffer (>= every row's prompt length)
-    int tail;              // prompt positions from <|startoftranscript|> to the end (3, or 4 with no-timestamps)
+    int tail;              // prompt positions from <|startoftranscript|> to the end (3, or 4 with no-timestamps;
+                           // English-only models: 1, or 2 with no-timestamps)
+    int sot_last;          // 1: <|startoftranscript|> ends every row's prompt (English-only with timestamps), so
+                           // the first sampled step also records the no-speech prob (select.h sot_sample_step)
     int V, eot, no_speech, no_ts, tb, blank, first_lang, n_langs;
     int suppress_blank, with_ts, max_init_ts;
     int beam;              // hypotheses per window (1 = greedy)

@@ -721,6 +721,7 @@ __device__ __forceinline__ void beam_slice_body(const float* __restrict__ logits
         mw[u] = supmask[v >> 5];
     }
     const RowRules R = row_rules(P, s);
+    const bool comb = sot_sample_step(P, SEL_SAMPLE, s);
     float m_all = -INFINITY, s_all = 0.f, m_ts = -INFINITY, s_ts = 0.f;
     ArgMax a_all{-INFINITY, 0x7fffffff}, a_text{-INFINITY, 0x7fffffff}, a_ts{-INFINITY, 0x7fffffff};
     unsigned okA = 0, okB = 0, live = 0;  // allowed / allowed timestamp / in slice and not NaN
@@ -729,11 +730,16 @@ __device__ __forceinline__ void beam_slice_body(const float* __restrict__ logits
         const int v = lo + u * 256 + tid;
         if (v >= hi) continue;
         if (xv[u] == xv[u]) live |= 1u << u;
+        if (comb) {  // raw statistics in the timestamp slots (select.h sot_sample_step); list B stays empty
+            lse_add(m_ts, s_ts, xv[u]);
+            if (v == P.no_speech) a_text = ArgMax{xv[u], v};
+        }
         if (tok_masked_w(P, R, mw[u], v)) continue;
         const float xu = xv[u];
         lse_add(m_all, s_all, xu);
         a_all = amax(a_all, ArgMax{xu, v});
         okA |= 1u << u;
+        if (comb) continue;
         if (v >= P.tb) {
             lse_add(m_ts, s_ts, xu);
             a_ts = amax(a_ts, ArgMax{xu, v});
@@ -1156,9 +1162,13 @@ __device__ __forceinline__ void beam_update_body(const SelParams& P, const int* 
             const int k = tid / SEL_SPLIT;
             const float lse_all = m_all + logf(s_all);
             const float lse_ts = m_ts == -INFINITY ? -INFINITY : m_ts + logf(s_ts);
-            const bool ts_wins = P.with_ts && lse_ts - lse_all > X.v - lse_all;
+            // (the combined step of an English-only row: the timestamp slots hold the raw
+            // statistics, every candidate of list A is a timestamp, no mass rule to apply)
+            const bool comb = first && P.sot_last;
+            const bool ts_wins = !comb && P.with_ts && lse_ts - lse_all > X.v - lse_all;
             rlse[k] = ts_wins ? lse_ts : lse_all;
             rts[k] = ts_wins;
+            if (comb && k == 0) lst[0].nsp = __expf(X.v - lse_ts);  // every hypothesis descends from row 0
         }
         if (tid < K) rsum[tid] = ms.sum_lp;
     }

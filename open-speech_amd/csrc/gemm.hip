@@ -1614,6 +1614,13 @@ __device__ __forceinline__ void fused_select_row(float x, int col, bool valid, c
         if (mode == SEL_SOT) {
             lse_add(r.m_all, r.s_all, x);
             if (v >= P.first_lang && v < P.first_lang + P.n_langs) a_text = ArgMax{x, v};
+        } else if (sot_sample_step(P, mode, s)) {  // raw statistics beside the masked ones (select.h)
+            lse_add(r.m_ts, r.s_ts, x);
+            if (v == P.no_speech) a_text = ArgMax{x, v};
+            if (!tok_masked_w(P, row_rules(P, s), pre.supw, v)) {
+                lse_add(r.m_all, r.s_all, x);
+                a_all = ArgMax{x, v};
+            }
         } else if (!tok_masked_w(P, row_rules(P, s), pre.supw, v)) {
             lse_add(r.m_all, r.s_all, x);
             a_all = ArgMax{x, v};

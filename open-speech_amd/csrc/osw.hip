@@ -214,6 +214,7 @@ struct EncBaton {
 struct AlignBufs {
     int *slot = nullptr, *len = nullptr, *forced = nullptr, *lh = nullptr;  // per decoder row; {head, idx} pairs
     int *slot_len = nullptr, *slot_frames = nullptr, *slot_width = nullptr, *slot_T = nullptr, *path_len = nullptr;
+    int *head = nullptr, *slot_head = nullptr;  // per row / per slot: forced positions before the first kept row
     int *tf = nullptr, *path = nullptr;
     float *tokprob = nullptr /* log-probabilities */, *scores = nullptr, *stats = nullptr, *colstats = nullptr, *M = nullptr;
     unsigned char* trace = nullptr;
@@ -1155,14 +1156,44 @@ hipGraphExec_t decode_graph(osw_ctx* c, const std::vector<int64_t>& key, const s
 
 // Confidences (osw_set_confidences): the recording pointers of a decode's SelParams (all null
 // when off, so the kernels store nothing) ...
-void conf_params(const osw_ctx* c, SelParams& SP, int group) {
+void conf_params(const osw_ctx* c, SelParams& SP, int group, bool english = false) {
     SP.lp_group = std::max(1, group);
     SP.lp_stride = c->d.n_text_ctx;
     if (!c->conf) return;
-    REQUIRE(SP.n_langs >= 1 && SP.n_langs <= LANG_CAP, "confidences hold at most 128 languages");
+    REQUIRE(english || (SP.n_langs >= 1 && SP.n_langs <= LANG_CAP), "confidences hold at most 128 languages");
     SP.lp_hist = c->lp_hist;
     SP.best_lp = c->best_lp;
-    SP.lang_probs = c->lang_probs;
+    SP.lang_probs = english ? nullptr : c->lang_probs;  // English-only: no language distribution
+}
+
+// The start sequence.  osw_decode_opts::task_token < 0 selects an English-only model's:
+// <|startoftranscript|> alone (faster-whisper's Tokenizer.sot_sequence for a model that is not
+// multilingual), so a prompt is [prefix..., sot(, no_timestamps)] and the language fields of
+// the options are ignored; otherwise [prefix..., sot, language, task(, no_timestamps)].
+struct StartSeq {
+    bool english;
+    int tail;  // prompt positions from <|startoftranscript|> to the end
+    int n_langs;  // language tokens the selection and the confidences see (0: English-only)
+};
+StartSeq start_seq(const osw_decode_opts* o) {
+    const bool en = o->task_token < 0;
+    return StartSeq{en, (en ? 1 : 3) + (o->without_timestamps ? 1 : 0), en ? 0 : o->n_langs};
+}
+// e[0 .. tail): the start sequence with `lang` as its language token (-1: detect)
+void start_tokens(const osw_decode_opts* o, const StartSeq& ss, int lang, int* e) {
+    int k = 0;
+    e[k++] = o->sot;
+    if (!ss.english) {
+        e[k++] = lang;
+        e[k++] = o->task_token;
+    }
+    if (o->without_timestamps) e[k++] = o->no_timestamps;
+}
+// the selection's view of it: with timestamps an English-only row samples at <|startoftranscript|>
+void start_params(SelParams& SP, const osw_decode_opts* o, const StartSeq& ss) {
+    SP.tail = ss.tail;
+    SP.sot_last = ss.english && !o->without_timestamps;
+    if (ss.english) SP.first_lang = 0, SP.n_langs = 0;
 }
 // ... and the read-back of one finished window into conf_res[i]: `cum` = the row's lp_hist (or the
 // window's best_lp), `nlp` its recorded entries, n0 / n the window's token count before / after
@@ -1243,7 +1274,8 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r, 
     REQUIRE(rows <= c->R, "windows x beam_size (best_of) exceeds the decoder row capacity (5 x max_batch)");
     REQUIRE(group == 1 || !r->logits_dump, "logits dump needs one decoder row per window");
     REQUIRE(V <= SEL_SPLIT * 4096, "vocabulary too large for the selection kernels");
-    const int P = n_pre + 3 + (o->without_timestamps ? 1 : 0);
+    const StartSeq ss = start_seq(o);
+    const int P = n_pre + ss.tail;
     const int max_len = std::min(o->max_length > 0 ? o->max_length : d.n_text_ctx, d.n_text_ctx);
     REQUIRE(P < max_len, "prompt longer than max_length");
     // one prompt per decoder row (the beam rows of a window share it)
@@ -1252,10 +1284,7 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r, 
         for (int k = 0; k < group; ++k) {
             int* pr = &prompt[((size_t)b * group + k) * P];
             for (int i = 0; i < n_pre; ++i) pr[i] = o->prefix_tokens[(size_t)b * n_pre + i];
-            pr[n_pre] = o->sot;
-            pr[n_pre + 1] = o->language_tokens ? o->language_tokens[b] : o->language_token;  // -1: detect
-            pr[n_pre + 2] = o->task_token;
-            if (o->without_timestamps) pr[n_pre + 3] = o->no_timestamps;
+            start_tokens(o, ss, o->language_tokens ? o->language_tokens[b] : o->language_token, pr + n_pre);
         }
     std::vector<unsigned> mask((V + 31) / 32, 0u);
     for (int i = 0; i < o->n_suppress; ++i) {
@@ -1281,9 +1310,10 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r, 
     }
     SelParams SP{};
     SP.prompt_len = P; SP.sot_pos = n_pre; SP.lang_pos = n_pre + 1; SP.max_length = max_len;
-    SP.pstride = P; SP.tail = P - n_pre;
+    SP.pstride = P;
     SP.V = V; SP.eot = o->eot; SP.no_speech = o->no_speech; SP.no_ts = o->no_timestamps; SP.tb = o->timestamp_begin;
     SP.blank = o->blank; SP.first_lang = o->first_lang; SP.n_langs = o->n_langs;
+    start_params(SP, o, ss);
     SP.suppress_blank = o->suppress_blank; SP.with_ts = o->without_timestamps ? 0 : 1;
     SP.max_init_ts = o->max_initial_timestamp_index;
     SP.beam = beam;
@@ -1301,7 +1331,7 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r, 
         SP.budget = c->budget;
     }
     c->conf_valid = false;
-    conf_params(c, SP, group);
+    conf_params(c, SP, group, ss.english);
     // history rules (repetition_penalty / no_repeat_ngram_size): per row, on the raw logits
     const HistRules hr = hist_rules(o, d);
     auto select = [&] {
@@ -1335,6 +1365,8 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r, 
                                     o->without_timestamps, o->max_initial_timestamp_index, beam, SP.num_hyp,
                                     SP.max_cand, lp_bits, group, it_bits, SP.budget ? 1 : 0, hr.penalty_bits(),
                                     hr.ngram, c->conf ? 1 : 0};
+        // (no multilingual key has this length with -3 last, nor a mapped one with -3 before its window count)
+        if (ss.english) key.push_back(-3);
         // a mapped decode bakes the map's address and the plane stride into its launches: its own
         // key (a longer one, so no plain key equals it); the map's contents are data, not key
         if (windows) key.push_back(c->n_encoded);
@@ -1392,10 +1424,11 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r, 
     std::vector<float> cum, lang;
     if (c->conf) {
         cum.resize((size_t)(beam > 1 ? nb : rows) * ctx);
-        lang.resize((size_t)nb * o->n_langs);
+        lang.resize((size_t)nb * ss.n_langs);
         HIPCHK(hipMemcpyAsync(cum.data(), beam > 1 ? c->best_lp : c->lp_hist, cum.size() * 4, hipMemcpyDeviceToHost,
                               c->stream));
-        HIPCHK(hipMemcpyAsync(lang.data(), c->lang_probs, lang.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        if (!lang.empty())
+            HIPCHK(hipMemcpyAsync(lang.data(), c->lang_probs, lang.size() * 4, hipMemcpyDeviceToHost, c->stream));
         c->conf_res.clear();
     }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1417,10 +1450,10 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r, 
         for (int i = 0; i < n; ++i) r->tokens[(size_t)b * r->max_tokens + i] = src[i];
         r->sum_logprob[b] = beam > 1 ? bw[b].best_raw : sp.sum_lp;
         r->no_speech_prob[b] = sp.nsp;
-        r->language[b] = sp.lang;
+        r->language[b] = ss.english ? -1 : sp.lang;
         if (c->conf)
             conf_store(c, b, &cum[(beam > 1 ? (size_t)b : best) * ctx], beam > 1 ? bw[b].best_nlp : sp.n_lp, n0, n,
-                       &lang[(size_t)b * o->n_langs], o->n_langs);
+                       lang.data() + (size_t)b * ss.n_langs, ss.n_langs);
     }
     c->conf_valid = c->conf;
 }
@@ -1433,6 +1466,7 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r, 
 void detect_language(osw_ctx* c, int nb, const osw_decode_opts* o, float* probs, float* raw) {
     REQUIRE(nb >= 1 && nb == c->n_encoded, "detect window count must equal the last encode call");
     REQUIRE(o && probs, "null detect argument");
+    REQUIRE(o->task_token >= 0, "an English-only model (task_token < 0) has no language to detect");
     const osw_dims& d = c->d;
     const int V = d.n_vocab, P = 3;
     REQUIRE(V <= SEL_SPLIT * 4096, "vocabulary too large for the selection kernels");
@@ -1526,6 +1560,8 @@ void align_reserve(osw_ctx* c, int n_slots, int pstride, int rows) {
         A.slot_frames = dalloc<int>(c->B, o);
         A.slot_width = dalloc<int>(c->B, o);
         A.slot_T = dalloc<int>(c->B, o);
+        A.head = dalloc<int>(c->R, o);
+        A.slot_head = dalloc<int>(c->B, o);
         A.path_len = dalloc<int>(c->B, o);
         A.tf = dalloc<int>((size_t)c->B * ctx, o);
         A.tokprob = dalloc<float>((size_t)c->B * ctx, o);
@@ -1560,7 +1596,7 @@ void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
     REQUIRE(n <= nb, "more windows than the last encode call holds");
     AlignBufs& A = c->al;
     std::vector<int> slot(nb, -1), len(nb, 0), forced((size_t)nb * ctx, 0);
-    std::vector<int> s_len, s_fr, s_w, s_T;
+    std::vector<int> s_len, s_fr, s_w, s_T, s_head, head(nb, 3);
     A.win.clear();
     A.T.clear();
     A.F.clear();
@@ -1571,7 +1607,12 @@ void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
         REQUIRE(a.window >= 0 && a.window < nb, "align: stale window index");
         REQUIRE(slot[a.window] < 0 && len[a.window] == 0, "align: a window appears twice");
         REQUIRE(a.n_tokens >= 0 && (a.n_tokens == 0 || a.tokens), "align: bad token list");
-        REQUIRE(a.n_tokens + 5 <= ctx, "align: forced sequence longer than n_text_ctx");
+        // language and task both negative: an English-only model's forced sequence
+        // [sot, no_timestamps, tokens..., eot] (find_alignment passes the tokenizer's sot_sequence)
+        REQUIRE((a.language < 0) == (a.task < 0), "align: language and task are both negative (English-only) or neither");
+        const bool en = a.language < 0;
+        const int hd = en ? 1 : 3;  // forced positions before <|notimestamps|>, the first kept row
+        REQUIRE(a.n_tokens + hd + 2 <= ctx, "align: forced sequence longer than n_text_ctx");
         REQUIRE(a.n_tokens + 1 <= r->stride, "align: result stride too small");
         REQUIRE(a.eot == eot && eot > 0 && eot < V, "align: one <|endoftext|> id per call");
         const int W = a.median_filter_width > 0 ? a.median_filter_width : 7;
@@ -1580,15 +1621,20 @@ void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
         if (a.n_tokens == 0) continue;  // no text: no work, empty results
         const int F = std::min(T_ENC, a.num_frames / 2);
         REQUIRE(F >= 1, "align: num_frames < 2");
-        for (int t : {a.sot, a.language, a.task, a.no_timestamps}) REQUIRE(t >= 0 && t < V, "align: bad special token");
+        for (int t : {a.sot, en ? a.sot : a.language, en ? a.sot : a.task, a.no_timestamps})
+            REQUIRE(t >= 0 && t < V, "align: bad special token");
         int* f = &forced[(size_t)a.window * ctx];
-        f[0] = a.sot; f[1] = a.language; f[2] = a.task; f[3] = a.no_timestamps;
+        f[0] = a.sot;
+        if (!en) f[1] = a.language, f[2] = a.task;
+        f[hd] = a.no_timestamps;
         for (int k = 0; k < a.n_tokens; ++k) {
             REQUIRE(a.tokens[k] >= 0 && a.tokens[k] < eot, "align: text tokens must be below <|endoftext|>");
-            f[4 + k] = a.tokens[k];
+            f[hd + 1 + k] = a.tokens[k];
         }
-        f[4 + a.n_tokens] = eot;
-        const int P = a.n_tokens + 5;
+        f[hd + 1 + a.n_tokens] = eot;
+        const int P = a.n_tokens + hd + 2;
+        head[a.window] = hd;
+        s_head.push_back(hd);
         slot[a.window] = (int)A.win.size();
         len[a.window] = P;
         A.win.push_back(a.window);
@@ -1624,6 +1670,8 @@ void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
     up(A.slot_frames, s_fr.data(), ns * 4);
     up(A.slot_width, s_w.data(), ns * 4);
     up(A.slot_T, s_T.data(), ns * 4);
+    up(A.head, head.data(), nb * 4);
+    up(A.slot_head, s_head.data(), ns * 4);
     up(c->sel, st.data(), nb * sizeof(SelState));
     up(c->cur_tok, first.data(), nb * 4);
     HIPCHK(hipMemsetAsync(c->pos, 0, 4, c->stream));
@@ -1638,8 +1686,8 @@ void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
     c->acap = &cap;
     auto one_step = [&] {
         decoder_step(c, nb, 1, false, nullptr);
-        launch_align_tail(c->logits, nb, V, eot, ctx, c->pos, A.slot, A.len, A.forced, A.tokprob, c->cur_tok, c->sel,
-                          c->stream);
+        launch_align_tail(c->logits, nb, V, eot, ctx, c->pos, A.slot, A.len, A.head, A.forced, A.tokprob, c->cur_tok,
+                          c->sel, c->stream);
         launch_align_bump(c->pos, c->stream);
     };
     const int CH = 8;
@@ -1657,8 +1705,8 @@ void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
         HIPCHK(hipGetLastError());
     }
     c->acap = nullptr;
-    launch_align_post(A.scores, ns, A.n_heads, pstride, A.slot_len, A.slot_frames, A.slot_width, A.stats, A.colstats,
-                      A.M, c->stream);
+    launch_align_post(A.scores, ns, A.n_heads, pstride, A.slot_len, A.slot_head, A.slot_frames, A.slot_width, A.stats,
+                      A.colstats, A.M, c->stream);
     launch_align_dtw(A.M, (int64_t)pstride * T_ENC, T_ENC, 1, ns, A.slot_T, A.slot_frames, A.trace,
                      (int64_t)pstride * (T_ENC + 1), A.path, pstride + T_ENC, A.path_len, A.tf, ctx, c->stream);
     HIPCHK(hipGetLastError());
@@ -1694,7 +1742,8 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
     REQUIRE(V <= SEL_SPLIT * 4096, "vocabulary too large for the selection kernels");
     const int R = c->B;
     REQUIRE(R <= c->R, "decoder rows");
-    const int P = 3 + (o->without_timestamps ? 1 : 0);
+    const StartSeq ss = start_seq(o);
+    const int P = ss.tail;
     const int max_len = std::min(o->max_length > 0 ? o->max_length : d.n_text_ctx, d.n_text_ctx);
     REQUIRE(P < max_len, "prompt longer than max_length");
     const int max_tok = std::max(1, max_len - P);
@@ -1706,9 +1755,10 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
     }
     SelParams SP{};
     SP.prompt_len = P; SP.sot_pos = 0; SP.lang_pos = 1; SP.max_length = max_len;
-    SP.pstride = P; SP.tail = P;
+    SP.pstride = P;
     SP.V = V; SP.eot = o->eot; SP.no_speech = o->no_speech; SP.no_ts = o->no_timestamps; SP.tb = o->timestamp_begin;
     SP.blank = o->blank; SP.first_lang = o->first_lang; SP.n_langs = o->n_langs;
+    start_params(SP, o, ss);
     SP.suppress_blank = o->suppress_blank; SP.with_ts = o->without_timestamps ? 0 : 1;
     SP.max_init_ts = o->max_initial_timestamp_index;
     SP.beam = 1; SP.num_hyp = 1; SP.max_cand = 1;
@@ -1720,7 +1770,7 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
     SP.pos_row = 1;
     c->conf_valid = false;
     c->conf_res.clear();
-    conf_params(c, SP, 1);
+    conf_params(c, SP, 1, ss.english);
     const HistRules hr = hist_rules(o, d);
     HIPCHK(hipMemcpyAsync(c->supmask, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, c->stream));
     // every row starts finished (nothing to step until a window is admitted)
@@ -1749,16 +1799,17 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
         int32_t lp_bits;
         std::memcpy(&lp_bits, &SP.length_penalty, 4);
         // (the -1 tail keeps refill keys apart from decode()'s)
-        const std::vector<int64_t> key = {R, P, 0, max_len, o->eot, o->no_speech, o->no_timestamps,
-                                          o->timestamp_begin, o->blank, o->first_lang, o->n_langs, o->suppress_blank,
-                                          o->without_timestamps, o->max_initial_timestamp_index, 1, 1,
-                                          1, lp_bits, 1, 0, SP.budget ? 1 : 0, -1, hr.penalty_bits(), hr.ngram,
-                                          c->conf ? 1 : 0};
+        std::vector<int64_t> key = {R, P, 0, max_len, o->eot, o->no_speech, o->no_timestamps,
+                                    o->timestamp_begin, o->blank, o->first_lang, o->n_langs, o->suppress_blank,
+                                    o->without_timestamps, o->max_initial_timestamp_index, 1, 1,
+                                    1, lp_bits, 1, 0, SP.budget ? 1 : 0, -1, hr.penalty_bits(), hr.ngram,
+                                    c->conf ? 1 : 0};
+        if (ss.english) key.push_back(-3);
         ge = decode_graph(c, key, one_step, CH);
     }
     std::vector<int> row_clip(R, -1), pack, toks((size_t)R * max_tok);
     const int ctx = d.n_text_ctx;
-    std::vector<float> cum(c->conf ? (size_t)R * ctx : 0), lang(c->conf ? (size_t)R * o->n_langs : 0);
+    std::vector<float> cum(c->conf ? (size_t)R * ctx : 0), lang(c->conf ? (size_t)R * ss.n_langs : 0);
     int next = 0, active = 0, steps = 0;
     while (true) {
         std::vector<int> free_rows;
@@ -1777,10 +1828,7 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
                 int* e = &pack[(size_t)i * (2 + P)];
                 e[0] = row;
                 e[1] = o->token_budget ? o->token_budget[clip] : 0;
-                e[2] = o->sot;
-                e[3] = o->language_tokens ? o->language_tokens[clip] : o->language_token;  // -1: detect
-                e[4] = o->task_token;
-                if (o->without_timestamps) e[5] = o->no_timestamps;
+                start_tokens(o, ss, o->language_tokens ? o->language_tokens[clip] : o->language_token, e + 2);
                 row_clip[row] = clip;
             }
             encode(c, wins.data(), k, slots.data());
@@ -1809,7 +1857,8 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
         HIPCHK(hipMemcpyAsync(toks.data(), c->tokens, toks.size() * 4, hipMemcpyDeviceToHost, c->stream));
         if (c->conf) {
             HIPCHK(hipMemcpyAsync(cum.data(), c->lp_hist, cum.size() * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(lang.data(), c->lang_probs, lang.size() * 4, hipMemcpyDeviceToHost, c->stream));
+            if (!lang.empty())
+                HIPCHK(hipMemcpyAsync(lang.data(), c->lang_probs, lang.size() * 4, hipMemcpyDeviceToHost, c->stream));
         }
         HIPCHK(hipStreamSynchronize(c->stream));
         for (int i = 0; i < R; ++i) {
@@ -1821,10 +1870,10 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
             for (int j = 0; j < n; ++j) r->tokens[(size_t)clip * r->max_tokens + j] = toks[(size_t)i * max_tok + j];
             r->sum_logprob[clip] = q.sum_lp;
             r->no_speech_prob[clip] = q.nsp;
-            r->language[clip] = q.lang;
+            r->language[clip] = ss.english ? -1 : q.lang;
             if (c->conf)
-                conf_store(c, clip, &cum[(size_t)i * ctx], q.n_lp, q.n_sampled, n, &lang[(size_t)i * o->n_langs],
-                           o->n_langs);
+                conf_store(c, clip, &cum[(size_t)i * ctx], q.n_lp, q.n_sampled, n, lang.data() + (size_t)i * ss.n_langs,
+                           ss.n_langs);
             row_clip[i] = -1;
             --active;
         }
@@ -2180,7 +2229,8 @@ void session_begin(osw_ctx* c, const osw_decode_opts* o) {
     REQUIRE(S->beam <= 5, "decode sessions hold beam_size <= 5 (5 decoder rows per window slot)");
     S->W = c->B;
     S->ctx = d.n_text_ctx;
-    S->tail = 3 + (o->without_timestamps ? 1 : 0);
+    const StartSeq ss = start_seq(o);
+    S->tail = ss.tail;
     S->max_len = std::min(o->max_length > 0 ? o->max_length : d.n_text_ctx, d.n_text_ctx);
     REQUIRE(S->tail < S->max_len, "prompt longer than max_length");
     S->max_tok = std::max(1, S->max_len - S->tail);
@@ -2191,9 +2241,10 @@ void session_begin(osw_ctx* c, const osw_decode_opts* o) {
     }
     SelParams& SP = S->SP;
     SP.prompt_len = S->tail; SP.sot_pos = 0; SP.lang_pos = 1; SP.max_length = S->max_len;
-    SP.pstride = S->ctx; SP.tail = S->tail;
+    SP.pstride = S->ctx;
     SP.V = V; SP.eot = o->eot; SP.no_speech = o->no_speech; SP.no_ts = o->no_timestamps; SP.tb = o->timestamp_begin;
     SP.blank = o->blank; SP.first_lang = o->first_lang; SP.n_langs = o->n_langs;
+    start_params(SP, o, ss);
     SP.suppress_blank = o->suppress_blank; SP.with_ts = o->without_timestamps ? 0 : 1;
     SP.max_init_ts = o->max_initial_timestamp_index;
     SP.beam = S->beam;
@@ -2206,7 +2257,7 @@ void session_begin(osw_ctx* c, const osw_decode_opts* o) {
     SP.budget = c->budget;
     SP.pos_row = 1;
     c->conf_valid = false;
-    conf_params(c, SP, S->beam);  // (osw_set_confidences is refused while the session is open)
+    conf_params(c, SP, S->beam, ss.english);  // (osw_set_confidences is refused while the session is open)
     S->o.suppress_tokens = nullptr;  // (copied into the mask)
     S->o.prefix_tokens = nullptr;
     S->o.language_tokens = nullptr;
@@ -2346,10 +2397,7 @@ void session_admit(osw_ctx* c, int refill_min) {
         e[1] = np + S->tail;
         e[2] = q.w.token_budget;
         for (int j = 0; j < np; ++j) e[3 + j] = q.prefix[j];
-        e[3 + np] = S->o.sot;
-        e[3 + np + 1] = q.w.language_token;  // -1: detect
-        e[3 + np + 2] = S->o.task_token;
-        if (S->o.without_timestamps) e[3 + np + 3] = S->o.no_timestamps;
+        start_tokens(&S->o, start_seq(&S->o), q.w.language_token, e + 3 + np);
     }
     encode(c, wins.data(), k, slots.data());
     for (int i = 0; i < k; ++i) S->slot_tag[free_slots[i]] = S->queue[i].w.tag;
@@ -2411,12 +2459,13 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
             int32_t lp_bits;
             std::memcpy(&lp_bits, &SP.length_penalty, 4);
             // (the -2 tail keeps session keys apart from decode()'s and the refill's)
-            const std::vector<int64_t> key = {nb, S->tail, 0, S->max_len, S->o.eot, S->o.no_speech, S->o.no_timestamps,
+            std::vector<int64_t> key = {nb, S->tail, 0, S->max_len, S->o.eot, S->o.no_speech, S->o.no_timestamps,
                                               S->o.timestamp_begin, S->o.blank, S->o.first_lang, S->o.n_langs,
                                               S->o.suppress_blank, S->o.without_timestamps,
                                               S->o.max_initial_timestamp_index, beam, SP.num_hyp, SP.max_cand, lp_bits,
                                               beam, 0, 1, -2, CH, S->hr.penalty_bits(), S->hr.ngram,
                                               c->conf ? 1 : 0};
+            if (S->o.task_token < 0) key.push_back(-3);
             hipGraphExec_t ge = decode_graph(c, key, one_step, CH);
             trace_graph(c, "launch");
             HIPCHK(hipGraphLaunch(ge, c->stream));
@@ -2440,14 +2489,15 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
         std::vector<int> toks((size_t)hi * S->max_tok);
         HIPCHK(hipMemcpyAsync(toks.data(), beam > 1 ? c->btok : c->tokens, toks.size() * 4, hipMemcpyDeviceToHost,
                               c->stream));
-        const int n_langs = S->o.n_langs;
+        const int n_langs = start_seq(&S->o).n_langs;
         std::vector<float> cum, lang;
         if (c->conf) {  // beam: the best hypothesis' history per window slot; greedy: the rows' own
             cum.resize((size_t)hi * S->ctx);
             lang.resize((size_t)hi * n_langs);
             HIPCHK(hipMemcpyAsync(cum.data(), beam > 1 ? c->best_lp : c->lp_hist, cum.size() * 4, hipMemcpyDeviceToHost,
                                   c->stream));
-            HIPCHK(hipMemcpyAsync(lang.data(), c->lang_probs, lang.size() * 4, hipMemcpyDeviceToHost, c->stream));
+            if (!lang.empty())
+                HIPCHK(hipMemcpyAsync(lang.data(), c->lang_probs, lang.size() * 4, hipMemcpyDeviceToHost, c->stream));
         }
         HIPCHK(hipStreamSynchronize(c->stream));
         for (int slot : fin) {
@@ -2458,10 +2508,10 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
             for (int j = 0; j < n; ++j) r->tokens[(size_t)done * r->max_tokens + j] = toks[(size_t)slot * S->max_tok + j];
             r->sum_logprob[done] = beam > 1 ? bw[slot].best_raw : q.sum_lp;
             r->no_speech_prob[done] = q.nsp;
-            r->language[done] = q.lang;
+            r->language[done] = S->o.task_token < 0 ? -1 : q.lang;
             if (c->conf)
                 conf_store(c, done, &cum[(size_t)slot * S->ctx], beam > 1 ? bw[slot].best_nlp : q.n_lp, n0, n,
-                           &lang[(size_t)slot * n_langs], n_langs);
+                           lang.data() + (size_t)slot * n_langs, n_langs);
             tags[done] = S->slot_tag[slot];
             S->slot_tag[slot] = -1;
             --S->active;
@@ -2813,6 +2863,8 @@ int osw_get_language_probs(osw_ctx* c, int32_t i, float* probs, int32_t n_langs)
         REQUIRE(c && probs, "null argument");
         std::lock_guard<std::mutex> lk(c->mu);
         const osw_ctx::ConfResult& q = *conf_result(c, i);
+        if (q.lang.empty())
+            throw OswError(OSW_ESTATE, "an English-only decode (task_token < 0) records no language probabilities");
         REQUIRE(n_langs == (int32_t)q.lang.size(), "n_langs differs from the decode call's");
         std::copy(q.lang.begin(), q.lang.end(), probs);
     });

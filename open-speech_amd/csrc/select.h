@@ -53,6 +53,17 @@ __device__ __forceinline__ int sel_mode(const SelParams& P, int step, const SelS
     }
     return s.done ? SEL_DONE : SEL_SAMPLE;
 }
+// English-only models with timestamps: <|startoftranscript|> is the last prompt position, so
+// the row's first sampled step is also its no-speech step (SelParams::sot_last).  The slice
+// statistics of that one step carry both: every rule-allowed token is a timestamp there
+// (tok_masked_w masks all text at n_sampled == 0), so the timestamp slots would only repeat
+// m_all / s_all / a_all and hold instead
+//   m_ts/s_ts : the online log-sum-exp over the RAW logits (every entry, masked or not)
+//   a_text    : the raw <|nospeech|> logit (from the slice that holds it)
+// and the finalisers take lse_ts = lse_all there.  No other step's statistics change.
+__device__ __forceinline__ bool sot_sample_step(const SelParams& P, int mode, const SelState& s) {
+    return P.sot_last && mode == SEL_SAMPLE && s.n_sampled == 0;
+}
 
 // The logits rules for one row at its current state (SuppressBlank, SuppressTokens,
 // ApplyTimestampRules without the mass rule, which needs the slice statistics).
@@ -136,6 +147,7 @@ __device__ __forceinline__ void select_partial_body(const float* __restrict__ lo
     const int per = (P.V + SEL_SPLIT - 1) / SEL_SPLIT;
     const int lo = sl * per, hi = min(P.V, lo + per);
     const RowRules R = row_rules(P, s);
+    const bool comb = sot_sample_step(P, mode, s);
     float m_all = -INFINITY, s_all = 0.f, m_ts = -INFINITY, s_ts = 0.f;
     ArgMax a_all{-INFINITY, 0x7fffffff}, a_text{-INFINITY, 0x7fffffff}, a_ts{-INFINITY, 0x7fffffff};
     const unsigned long long seed = SAMPLE ? *P.seed : 0ull;
@@ -160,6 +172,15 @@ __device__ __forceinline__ void select_partial_body(const float* __restrict__ lo
             if (mode == SEL_SOT) {
                 lse_add(m_all, s_all, xv);
                 if (v >= P.first_lang && v < P.first_lang + P.n_langs) a_text = amax(a_text, ArgMax{xv, v});
+                continue;
+            }
+            if (comb) {  // the combined step: raw statistics beside the masked ones
+                lse_add(m_ts, s_ts, xv);
+                if (v == P.no_speech) a_text = ArgMax{xv, v};
+                if (tok_masked_w(P, R, ws[j], v)) continue;
+                lse_add(m_all, s_all, xv);
+                const float key = SAMPLE ? xv * P.inv_temp + gumbel_noise(seed, b, step, v) : xv;
+                a_all = amax(a_all, ArgMax{key, v});
                 continue;
             }
             if (tok_masked_w(P, R, ws[j], v)) continue;
@@ -290,7 +311,11 @@ __device__ __forceinline__ void select_finalize(const float* __restrict__ logits
     const int n = s.n_sampled;
     int next = r.i_all;
     float lse = lse_all;
-    if (P.with_ts) {
+    if (sot_sample_step(P, mode, s)) {
+        // the combined step: no-speech prob from the raw statistics, then the pick among the
+        // allowed tokens (all timestamps: no mass rule to apply)
+        s.nsp = __expf(r.v_text - (r.m_ts + __logf(r.s_ts)));
+    } else if (P.with_ts) {
         const float lse_ts = r.m_ts == -INFINITY ? -INFINITY : r.m_ts + __logf(r.s_ts);
         if (lse_ts - lse_all > r.v_text - lse_all) {  // timestamp mass wins: text suppressed
             next = r.i_ts;

@@ -49,19 +49,30 @@ TINY_TEST = WhisperDims(n_mels=80, n_audio_state=384, n_audio_head=6, n_audio_la
 MICRO_TEST = WhisperDims(n_mels=80, n_audio_state=128, n_audio_head=2, n_audio_layer=2,
                          n_text_state=128, n_text_head=2, n_text_layer=2)
 
+# TINY_TEST with the vocabulary of the English-only checkpoints (tiny.en ... medium.en)
+TINY_EN_TEST = WhisperDims(n_mels=80, n_audio_state=384, n_audio_head=6, n_audio_layer=4,
+                           n_vocab=51864, n_text_state=384, n_text_head=6, n_text_layer=4)
+
 PRESETS = {
     "large-v3-turbo": LARGE_V3_TURBO,
     "tiny-test": TINY_TEST,
+    "tiny-en-test": TINY_EN_TEST,
     "micro-test": MICRO_TEST,
 }
+
+ENGLISH_ONLY_VOCAB = 51864
 
 
 @dataclass(frozen=True)
 class SpecialTokens:
-    """Special token ids of the multilingual Whisper vocabulary.
+    """Special token ids of a Whisper vocabulary.
 
     For n_vocab == 51866 (large-v3 / turbo) the language block has 100 entries
     (``<|yue|>`` added), shifting every id after it by one relative to v2.
+    n_vocab == 51864 is the English-only vocabulary (``tiny.en`` ... ``medium.en``): its GPT-2
+    text part has one token fewer, so every special id sits one lower than at 51865; the 99
+    language tokens are present but never used, and ``multilingual`` is False (the start
+    sequence is <|startoftranscript|> alone).  Other sizes keep the multilingual ids.
     """
     eot: int
     sot: int
@@ -75,16 +86,19 @@ class SpecialTokens:
     no_timestamps: int
     timestamp_begin: int
     blank: int = 220  # tokenizer.encode(" ") for the GPT-2 derived BPE
+    multilingual: bool = True
 
     @classmethod
     def for_vocab(cls, n_vocab: int) -> "SpecialTokens":
         n_langs = 100 if n_vocab >= 51866 else 99
-        first_lang = 50259
+        english = n_vocab == ENGLISH_ONLY_VOCAB
+        eot = 50256 if english else 50257
+        first_lang = eot + 2
         after = first_lang + n_langs
-        return cls(eot=50257, sot=50258, first_lang=first_lang, n_langs=n_langs,
+        return cls(eot=eot, sot=eot + 1, first_lang=first_lang, n_langs=n_langs,
                    translate=after, transcribe=after + 1, sot_lm=after + 2,
                    sot_prev=after + 3, no_speech=after + 4, no_timestamps=after + 5,
-                   timestamp_begin=after + 6)
+                   timestamp_begin=after + 6, multilingual=not english)
 
 
 # Language codes in token order (openai-whisper tokenizer.LANGUAGES order).

@@ -224,7 +224,8 @@ class WhisperEngine:
         else:
             pre = np.zeros(1, np.int32)
             n_pre = 0
-        task = st.transcribe if cfg.task == "transcribe" else st.translate
+        # an English-only model: the start sequence is <|startoftranscript|> alone (osw.h: task_token < 0)
+        task = -1 if not st.multilingual else st.transcribe if cfg.task == "transcribe" else st.translate
         o = _lib.osw_decode_opts(
             task_token=task, language_token=-1 if cfg.language_token is None else int(cfg.language_token),
             suppress_blank=int(cfg.suppress_blank), without_timestamps=int(cfg.without_timestamps),
@@ -286,9 +287,11 @@ class WhisperEngine:
             cnt = C.c_int32()
             _lib.check(self.lib.osw_get_token_logprobs(self.ctx, i, cum.ctypes.data_as(f32p), len(cum),
                                                        C.byref(cnt)), "osw_get_token_logprobs")
-            probs = np.zeros(self.st.n_langs, np.float32)
-            _lib.check(self.lib.osw_get_language_probs(self.ctx, i, probs.ctypes.data_as(f32p), len(probs)),
-                       "osw_get_language_probs")
+            probs = None
+            if self.st.multilingual:
+                probs = np.zeros(self.st.n_langs, np.float32)
+                _lib.check(self.lib.osw_get_language_probs(self.ctx, i, probs.ctypes.data_as(f32p), len(probs)),
+                           "osw_get_language_probs")
             out.cum_logprobs = cum[:cnt.value].copy()
             out.token_logprobs, out.eot_logprob = split_cumulative(out.cum_logprobs, len(out.tokens))
             out.language_probs = probs
@@ -298,6 +301,8 @@ class WhisperEngine:
         (osw_detect_language: one decoder step on <|startoftranscript|>; replaces
         ``WhisperModel.detect_language``).  A later ``decode`` of the same windows is not
         affected.  ``return_logits``: also the raw logits the softmax was taken over."""
+        if not self.st.multilingual:
+            raise ValueError("an English-only model has no language to detect (its language is 'en')")
         o, keep = self._opts(DecodeConfig(), n, None)
         f32p = C.POINTER(C.c_float)
         probs = np.zeros((n, self.st.n_langs), np.float32)
@@ -457,9 +462,11 @@ class WhisperEngine:
         toks = [np.ascontiguousarray(w.tokens if len(w.tokens) else [0], dtype=np.int32) for w in windows]
         arr = (_lib.osw_align_window * len(windows))()
         for i, w in enumerate(windows):
+            # an English-only model forces [sot, no_timestamps, tokens..., eot] (language and task < 0)
             arr[i] = _lib.osw_align_window(
-                window=int(w.window), sot=st.sot, language=int(w.language),
-                task=st.transcribe if w.task == "transcribe" else st.translate, no_timestamps=st.no_timestamps,
+                window=int(w.window), sot=st.sot, language=int(w.language) if st.multilingual else -1,
+                task=-1 if not st.multilingual else st.transcribe if w.task == "transcribe" else st.translate,
+                no_timestamps=st.no_timestamps,
                 eot=st.eot, tokens=_i32p(toks[i]), n_tokens=len(w.tokens), num_frames=int(w.num_frames),
                 median_filter_width=int(w.median_filter_width))
         tf = np.zeros((len(windows), stride), np.int32)

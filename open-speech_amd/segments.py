@@ -240,10 +240,12 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
                      suppress: tuple) -> list[ClipResult]:
     """Run the seek loop for a batch of int16 clips on one engine (all share `opts`)."""
     st = tok.special
+    if opts.detect_only and not st.multilingual:  # nothing to detect: no engine call at all
+        return [_english_clip(ClipResult(duration=len(p) / 16000.0), True) for p in pcm_list]
     nf = engine.log_mel(pcm_list)
     if opts.detect_only:
         return _detect_clips(engine, pcm_list, nf, tok)
-    lang_token = tok.language_token(opts.language) if (opts.language and opts.task == "transcribe") else None
+    lang_token = _given_language(opts, tok)
     init_tokens = tok.encode(" " + opts.initial_prompt.strip()) if opts.initial_prompt else []
     states = []
     for i, n in enumerate(nf):
@@ -252,6 +254,8 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
         s.done = s.content_frames <= 0
         if lang_token is not None:
             s.result.language_probability = 1.0
+        if not st.multilingual:
+            _english_clip(s.result, bool(opts.token_logprobs))
         states.append(s)
     max_init = int(round(opts.max_initial_timestamp / TIME_PRECISION))
     temps = opts.temperatures
@@ -280,10 +284,12 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
                     size = min(N_FRAMES, s.content_frames - s.seek)
                     wins.append((s.idx, s.seek, size))
                 engine.encode(wins)
-                langs = None if _detect else [s.lang_token for s, _ in chunk]
+                # (an English-only model's start sequence has no language token: nothing to name)
+                langs = None if (_detect or not st.multilingual) else [s.lang_token for s, _ in chunk]
                 max_length = 448
                 if opts.max_new_tokens is not None:
-                    max_length = _plen + 3 + (1 if opts.without_timestamps else 0) + int(opts.max_new_tokens)
+                    max_length = (_plen + _start_len(st) + (1 if opts.without_timestamps else 0) +
+                                  int(opts.max_new_tokens))
                     if max_length > 448:
                         raise ValueError(f"the prompt is {max_length - int(opts.max_new_tokens)} tokens and "
                                          f"max_new_tokens is {opts.max_new_tokens}: their sum exceeds the "
@@ -321,9 +327,10 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
                 from .engine import AlignWindow
                 plans = [_plan(s, w, out, opts, tok, t) for (s, _), w, out, t in zip(chunk, wins, outs, win_temps)]
                 req = [(i, p) for i, p in enumerate(plans) if p is not None and p["text_tokens"]]
-                # the forced sequence adds 5 positions: a window that decoded more text tokens than
-                # fit (a model that never emits <|endoftext|>) aligns the ones that do
-                room = 448 - 5
+                # the forced sequence adds 5 positions (3 for an English-only model): a window that
+                # decoded more text tokens than fit (a model that never emits <|endoftext|>) aligns
+                # the ones that do
+                room = 448 - (_start_len(st) + 2)
                 als = engine.align([AlignWindow(window=i, tokens=p["text_tokens"][:room], num_frames=wins[i][2],
                                                 language=outs[i].language, task=opts.task)
                                     for i, p in req]) if req else []
@@ -375,7 +382,8 @@ def _fallback(engine, chunk: list, outs0: list, prefixes, attempt_cfg, temps: tu
             which = failing
             outs = engine.decode(len(which), attempt_cfg(k, which),
                                  prefix=[prefixes[i] for i in which] if prefixes else None,
-                                 languages=[chunk[i][0].lang_token for i in which], windows=list(which))
+                                 languages=[chunk[i][0].lang_token for i in which] if tok.special.multilingual
+                                 else None, windows=list(which))
         failing = []
         for i, out in zip(which, outs):
             avg = out.sum_logprob / (len(out.tokens) + 1)
@@ -403,6 +411,31 @@ def _set_language_probs(res: ClipResult, probs, lang_token: int, tok: WhisperTok
     res.language_probability = float(p[lang_token - tok.special.first_lang])
     res.all_language_probs = [(tok.language_code(tok.special.first_lang + int(i)), float(p[i]))
                               for i in np.argsort(-p, kind="stable")]
+
+
+ENGLISH_LANG = -1  # _ClipState.lang_token of an English-only model's clips: known, and no token
+
+
+def _given_language(opts: TranscribeOptions, tok: WhisperTokenizer):
+    """The clips' language token when the options name the language (None: detect it)."""
+    if not tok.special.multilingual:
+        return ENGLISH_LANG
+    return tok.language_token(opts.language) if (opts.language and opts.task == "transcribe") else None
+
+
+def _start_len(st) -> int:
+    """Tokens of the start sequence: sot, language, task; an English-only model's is sot alone."""
+    return 3 if st.multilingual else 1
+
+
+def _english_clip(res: ClipResult, want_probs: bool) -> ClipResult:
+    """faster-whisper's TranscriptionInfo for a model that is not multilingual: "en" with
+    probability 1, never detected."""
+    res.language = "en"
+    res.language_probability = 1.0
+    if want_probs:
+        res.all_language_probs = [("en", 1.0)]
+    return res
 
 
 def _detect_clips(engine, pcm_list: list, nf: list, tok: WhisperTokenizer) -> list[ClipResult]:
@@ -452,7 +485,7 @@ def session_config(opts: TranscribeOptions, suppress: tuple) -> DecodeConfig:
 def clip_state(idx: int, pcm: np.ndarray, opts: TranscribeOptions, tok: WhisperTokenizer) -> _ClipState:
     """transcribe_clips' per-clip state (log_mel's frame count is len // 160 + 1, the
     content frames one fewer)."""
-    lang_token = tok.language_token(opts.language) if (opts.language and opts.task == "transcribe") else None
+    lang_token = _given_language(opts, tok)
     init_tokens = tok.encode(" " + opts.initial_prompt.strip()) if opts.initial_prompt else []
     s = _ClipState(idx=idx, content_frames=len(pcm) // HOP_LENGTH, all_tokens=list(init_tokens),
                    lang_token=lang_token)
@@ -460,6 +493,8 @@ def clip_state(idx: int, pcm: np.ndarray, opts: TranscribeOptions, tok: WhisperT
     s.done = s.content_frames <= 0
     if lang_token is not None:
         s.result.language_probability = 1.0
+    if not tok.special.multilingual:
+        _english_clip(s.result, bool(opts.token_logprobs))
     return s
 
 
@@ -469,7 +504,8 @@ def next_window(s: _ClipState, opts: TranscribeOptions, tok: WhisperTokenizer) -
     prefix = ([tok.special.sot_prev] + prev[-(448 // 2 - 1):]) if prev else []
     size = min(N_FRAMES, s.content_frames - s.seek)
     budget = int(np.ceil(opts.tokens_per_second * size * FRAME_SEC)) + 2 if opts.tokens_per_second else 0
-    return dict(seek=s.seek, segment_size=size, prefix=prefix, language_token=s.lang_token, token_budget=budget)
+    lang = s.lang_token if tok.special.multilingual else None  # (English-only: no language token)
+    return dict(seek=s.seek, segment_size=size, prefix=prefix, language_token=lang, token_budget=budget)
 
 
 def consume_window(s: _ClipState, win: dict, out, opts: TranscribeOptions, tok: WhisperTokenizer) -> None:

@@ -9,10 +9,13 @@ from it exactly as upstream does (symbols and their space-prefixed forms encoded
 to single tokens).  Without one, the multilingual Whisper table below is used —
 it is the text-token part of the published ``suppress_tokens`` list of the
 multilingual checkpoints' generation config (parity unpinned: there is no
-tokenizer in this image to recompute it).
+tokenizer in this image to recompute it).  The English-only vocabulary (51864 ids)
+numbers its text tokens differently, so without a ``tokenizer.json`` it has no
+non-speech set at all (a warning is logged once) rather than a wrong one.
 """
 from __future__ import annotations
 
+import logging
 import os
 import string
 import zlib
@@ -34,6 +37,8 @@ UNSPACED_LANGUAGES = frozenset({"zh", "ja", "th", "lo", "my", "yue"})
 
 
 _BYTE_DECODER: dict = {}
+log = logging.getLogger(__name__)
+_warned_no_table = False
 
 
 def _byte_decoder() -> dict:
@@ -155,6 +160,13 @@ class WhisperTokenizer:
 
     def non_speech_tokens(self) -> tuple:
         if self._tok is None:
+            if not self.special.multilingual:
+                global _warned_no_table
+                if not _warned_no_table:
+                    _warned_no_table = True
+                    log.warning("English-only vocabulary without a tokenizer.json: suppress_tokens -1 expands to "
+                                "the special tokens only (no non-speech symbol table for this vocabulary)")
+                return ()
             return NON_SPEECH_TOKENS_MULTILINGUAL
         result = {self.encode(" -")[0], self.encode(" '")[0]}
         for symbol in _SYMBOLS + list(_MISC):
@@ -164,10 +176,14 @@ class WhisperTokenizer:
         return tuple(sorted(result))
 
     def language_code(self, lang_token: int) -> str:
+        if not self.special.multilingual:
+            return "en"
         i = lang_token - self.special.first_lang
         return LANGUAGE_CODES[i] if 0 <= i < len(LANGUAGE_CODES) else "en"
 
-    def language_token(self, code: str) -> int:
+    def language_token(self, code: str) -> int | None:
+        if not self.special.multilingual:
+            return None  # an English-only start sequence has no language token
         try:
             i = LANGUAGE_CODES.index(code)
         except ValueError as e:
