@@ -1,0 +1,811 @@
+// The osw_debug_* entry points: single kernels and launch forms on host data, for the parity
+// tests and the probes.
+#include "ctx.h"
+
+extern "C" {
+
+int osw_debug_dtw(osw_ctx* c, const float* x, int32_t T, int32_t F, int32_t* text_idx, int32_t* time_idx,
+                  int32_t* len) {
+    return guard([&] {
+        REQUIRE(c && x && text_idx && time_idx && len, "null argument");
+        REQUIRE(T >= 1 && T <= ALIGN_DTW_ROWS && F >= 1 && F <= 4096, "DTW shape out of range");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        std::vector<void*> tmp;
+        const int pcap = T + F;
+        float* xd = dalloc<float>((size_t)T * F, tmp);
+        unsigned char* tr = dalloc<unsigned char>((size_t)(T + 1) * (F + 1), tmp);
+        int* ib = dalloc<int>((size_t)3 + 2 * pcap + T, tmp);  // T, F, path_len, path, token_frame
+        int hdr[3] = {T, F, 0};
+        hipError_t e = hipMemcpyAsync(xd, x, (size_t)T * F * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ib, hdr, sizeof(hdr), hipMemcpyHostToDevice, c->stream);
+        std::vector<int> back((size_t)3 + 2 * pcap);
+        if (e == hipSuccess) {
+            launch_align_dtw(xd, 0, F, 0, 1, ib, ib + 1, tr, 0, ib + 3, pcap, ib + 2, ib + 3 + 2 * pcap, T, c->stream);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(back.data(), ib, back.size() * 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        dfree(xd, tmp);
+        dfree(tr, tmp);
+        dfree(ib, tmp);
+        HIPCHK(e);
+        const int k = back[2];
+        *len = k;
+        for (int i = 0; i < k; ++i) {
+            text_idx[i] = back[3 + pcap - k + i];
+            time_idx[i] = back[3 + pcap + pcap - k + i];
+        }
+    });
+}
+
+int osw_debug_history_rules(osw_ctx* c, float* logits, int32_t rows, int32_t V, const int32_t* tokens, int32_t stride,
+                            const int32_t* n_hist, float repetition_penalty, int32_t no_repeat_ngram_size) {
+    return guard([&] {
+        REQUIRE(c && logits && tokens && n_hist, "null argument");
+        REQUIRE(rows >= 1 && rows <= 65535 && V >= 1 && stride >= 1, "history rules shape out of range");
+        REQUIRE(stride <= c->d.n_text_ctx && stride <= 448, "history stride exceeds n_text_ctx");
+        for (int r = 0; r < rows; ++r) {
+            REQUIRE(n_hist[r] >= 0 && n_hist[r] <= stride, "history longer than its stride");
+            for (int i = 0; i < n_hist[r]; ++i)
+                REQUIRE(tokens[(size_t)r * stride + i] >= 0 && tokens[(size_t)r * stride + i] < V,
+                        "history token outside the vocabulary");
+        }
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        // every row samples at step 0 of a one-token prompt with n_hist[r] tokens behind it
+        SelParams SP{};
+        SP.prompt_len = 1;
+        SP.V = V;
+        std::vector<SelState> st(rows);
+        for (int r = 0; r < rows; ++r) {
+            st[r] = SelState{};
+            st[r].n_sampled = n_hist[r];
+        }
+        std::vector<void*> tmp;
+        float* xd = dalloc<float>((size_t)rows * V, tmp);
+        int* td = dalloc<int>((size_t)rows * stride + 1, tmp);  // histories, then the step counter
+        SelState* sd = dalloc<SelState>((size_t)rows, tmp);
+        const int zero = 0;
+        hipError_t e = hipMemcpyAsync(xd, logits, (size_t)rows * V * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(td, tokens, (size_t)rows * stride * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(td + (size_t)rows * stride, &zero, 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(sd, st.data(), (size_t)rows * sizeof(SelState), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && history_rules_on(repetition_penalty, no_repeat_ngram_size)) {
+            launch_history_rules(xd, rows, td + (size_t)rows * stride, SP, sd, td, stride, repetition_penalty,
+                                 no_repeat_ngram_size, c->stream);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(logits, xd, (size_t)rows * V * 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        dfree(xd, tmp);
+        dfree(td, tmp);
+        dfree(sd, tmp);
+        HIPCHK(e);
+    });
+}
+
+int osw_debug_history_rules_time(osw_ctx* c, int32_t rows, int32_t V, int32_t n_hist, float repetition_penalty,
+                                 int32_t no_repeat_ngram_size, int32_t iters, float* us) {
+    return guard([&] {
+        REQUIRE(c && us, "null argument");
+        REQUIRE(rows >= 1 && rows <= 65535 && V >= 4 && iters >= 1, "history rules shape out of range");
+        REQUIRE(n_hist >= 0 && n_hist <= c->d.n_text_ctx && n_hist <= 448, "history longer than n_text_ctx");
+        REQUIRE(history_rules_on(repetition_penalty, no_repeat_ngram_size), "both rules are off: nothing to time");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        const int stride = std::max(1, (int)n_hist);
+        SelParams SP{};
+        SP.prompt_len = 1;
+        SP.V = V;
+        std::vector<SelState> st(rows);
+        for (auto& q : st) q = SelState{}, q.n_sampled = n_hist;
+        std::vector<int> hist((size_t)rows * stride + 1, 0);  // period 3 (every thread's prefix matches), then the step counter
+        for (int r = 0; r < rows; ++r)
+            for (int i = 0; i < stride; ++i) hist[(size_t)r * stride + i] = 1 + i % 3;
+        std::vector<void*> tmp;
+        float* xd = dalloc<float>((size_t)rows * V, tmp);
+        int* td = dalloc<int>(hist.size(), tmp);
+        SelState* sd = dalloc<SelState>((size_t)rows, tmp);
+        hipEvent_t e0, e1;
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        try {
+            HIPCHK(hipMemsetAsync(xd, 0, (size_t)rows * V * 4, c->stream));
+            HIPCHK(hipMemcpyAsync(td, hist.data(), hist.size() * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(sd, st.data(), (size_t)rows * sizeof(SelState), hipMemcpyHostToDevice, c->stream));
+            auto run = [&] {
+                launch_history_rules(xd, rows, td + (size_t)rows * stride, SP, sd, td, stride, repetition_penalty,
+                                     no_repeat_ngram_size, c->stream);
+            };
+            run();  // warm
+            HIPCHK(hipEventRecord(e0, c->stream));
+            for (int i = 0; i < iters; ++i) run();
+            HIPCHK(hipEventRecord(e1, c->stream));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventSynchronize(e1));
+            float t = 0.f;
+            HIPCHK(hipEventElapsedTime(&t, e0, e1));
+            *us = t * 1e3f / iters;
+        } catch (...) {
+            (void)hipEventDestroy(e0);
+            (void)hipEventDestroy(e1);
+            for (void* p : tmp) (void)hipFree(p);
+            throw;
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        for (void* p : tmp) (void)hipFree(p);
+    });
+}
+
+int osw_encoder_layer_debug(osw_ctx* c, int32_t layer, const float* x, float* y, int32_t T) {
+    return guard([&] {
+        REQUIRE(c && x && y, "null argument");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        REQUIRE(c->finalized, "weights not finalized");
+        REQUIRE(T == T_ENC, "T must be 1500");
+        REQUIRE(layer >= 0 && layer < c->d.n_audio_layer, "layer out of range");
+        const int64_t n = (int64_t)T * c->d.n_audio_state;
+        HIPCHK(hipMemcpyAsync(c->X, x, n * 4, hipMemcpyHostToDevice, c->stream));
+        encoder_layer(c, layer, 1);
+        HIPCHK(hipMemcpyAsync(y, c->X, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        resolve_events(c);
+    });
+}
+
+int osw_debug_gemm(osw_ctx* c, int32_t M, int32_t N, int32_t K, int32_t variant, const void* A, const void* Wt,
+                   float* C, int32_t iters, float* ms) {
+    return guard([&] {
+        REQUIRE(c && A && Wt && C && ms, "null argument");
+        REQUIRE(M >= 1 && N >= 1 && K >= 64 && K % 64 == 0 && iters >= 1, "bad GEMM shape");
+        REQUIRE(variant != 3 || (M <= 64 && K % 128 == 0), "skinny needs M <= 64 and K % 128 == 0");
+        REQUIRE(variant < 8 || variant > 19 || variant == 11 || N % 8 == 0,
+                "the 8-phase debug variants need N % 8 == 0 (their epilogues store 8-column chunks)");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        std::vector<void*> tmp;
+        h16* dA = dalloc<h16>((size_t)M * K, tmp);
+        h16* dW = dalloc<h16>((size_t)N * K, tmp);
+        float* dC = dalloc<float>((size_t)M * N, tmp);
+        float* dP = variant == 3 ? dalloc<float>((size_t)skinny_ksplit(N, K) * M * N, tmp) : nullptr;
+        hipEvent_t e0, e1;
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        try {
+            HIPCHK(hipMemcpyAsync(dA, A, (size_t)M * K * 2, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(dW, Wt, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
+            GemmArgs g = gemm_plain(dA, K, dW, nullptr, M, N, K, dC, N, EPI_F32);
+            auto run = [&] {
+                if (variant == 3) launch_gemm_skinny(g, dP, c->stream);
+                else launch_gemm_variant(g, variant, c->stream);
+            };
+            run();  // warm
+            HIPCHK(hipEventRecord(e0, c->stream));
+            for (int i = 0; i < iters; ++i) run();
+            HIPCHK(hipEventRecord(e1, c->stream));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventSynchronize(e1));
+            float t = 0.f;
+            HIPCHK(hipEventElapsedTime(&t, e0, e1));
+            *ms = t / iters;
+            HIPCHK(hipMemcpyAsync(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        } catch (...) {
+            (void)hipEventDestroy(e0);
+            (void)hipEventDestroy(e1);
+            for (void* p : tmp) (void)hipFree(p);
+            throw;
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        for (void* p : tmp) (void)hipFree(p);
+    });
+}
+
+namespace {
+// temporary device buffers of one debug call: freed when the call ends, however it ends
+struct TmpBufs {
+    std::vector<void*> v;
+    ~TmpBufs() {
+        GateLock gate_(capture_gate());
+        for (void* p : v) (void)hipFree(p);
+    }
+};
+}  // namespace
+
+int osw_debug_enc_attn(osw_ctx* c, const void* qkv, int32_t nb, int32_t H, int32_t form, void* out) {
+    return guard([&] {
+        REQUIRE(c && qkv && out, "null argument");
+        REQUIRE(nb >= 1 && nb <= 64 && H >= 1 && H <= 20, "encoder attention shape out of range");
+        REQUIRE(form >= 0 && form < 16 && (form == 0 || (form & 1)), "form: 0 (auto) or 1 | 2 eager | 4 128-query | 8 pipelined");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t n = (size_t)nb * H * T_ENC * 64;
+        h16* dq = dalloc<h16>(3 * n, tmp.v);
+        h16* dout = dalloc<h16>(n, tmp.v);
+        HIPCHK(hipMemcpyAsync(dq, qkv, 3 * n * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemsetAsync(dout, 0xff, n * 2, c->stream));  // NaN: an unwritten element shows
+        if (form == 0) launch_enc_attn(dq, dout, T_ENC, H, nb, c->stream);
+        else launch_enc_attn_form(dq, dout, T_ENC, H, nb, (form & 2) != 0, !(form & 4), (form & 8) != 0, 1 << 30, c->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, dout, n * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
+namespace {
+// one cross-attention launch on host data; window_map null: K / V hold one window per row group
+// (kv_windows == rows / beam), else row group w attends window window_map[w] of kv_windows
+int debug_dec_xattn(osw_ctx* c, const float* q_slabs, int32_t ks, const float* bias, const void* K, const void* V,
+                    int32_t kv_windows, const int32_t* window_map, int32_t rows, int32_t beam, int32_t legacy,
+                    float* out) {
+    return guard([&] {
+        REQUIRE(c && q_slabs && K && V && out, "null argument");
+        REQUIRE(ks >= 1 && ks <= 32, "ks out of range");
+        REQUIRE(beam >= 1 && beam <= MAX_BEAM && rows >= beam && rows % beam == 0, "rows must be windows x beam, beam <= 8");
+        const int H = c->d.n_text_head, D = c->d.n_text_state, W = rows / beam;
+        REQUIRE(W <= c->B, "more windows than the context's max_batch (its arrival tickets)");
+        if (window_map) {
+            REQUIRE(kv_windows >= 1 && kv_windows <= c->B && W <= kv_windows, "window map: 1 <= row groups <= kv_windows <= max_batch");
+            std::vector<char> seen((size_t)kv_windows, 0);
+            for (int i = 0; i < W; ++i) {
+                REQUIRE(window_map[i] >= 0 && window_map[i] < kv_windows, "window map: index outside K / V");
+                REQUIRE(!seen[window_map[i]], "window map: a window appears twice");
+                seen[window_map[i]] = 1;
+            }
+        } else {
+            REQUIRE(kv_windows == W, "K / V hold one window per row group");
+        }
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t nq = (size_t)ks * rows * D, nkv = (size_t)kv_windows * H * T_ENC * 64, no = (size_t)rows * D;
+        float* dq = dalloc<float>(nq, tmp.v);
+        float* db = dalloc<float>(D, tmp.v);
+        h16* dk = dalloc<h16>(nkv, tmp.v);
+        h16* dv = dalloc<h16>(nkv, tmp.v);
+        h16* dout = dalloc<h16>(2 * no, tmp.v);  // hi, then lo
+        int* dmap = nullptr;
+        if (window_map) {
+            dmap = dalloc<int>((size_t)W, tmp.v);
+            HIPCHK(hipMemcpyAsync(dmap, window_map, (size_t)W * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        float* ws = legacy ? nullptr : dalloc<float>((size_t)rows * H * XCHUNKS * XPART, tmp.v);
+        SelState* st = dalloc<SelState>((size_t)rows, tmp.v);
+        HIPCHK(hipMemcpyAsync(dq, q_slabs, nq * 4, hipMemcpyHostToDevice, c->stream));
+        // the chunk kernels read the bias unconditionally: "none" is a zero bias for them
+        if (bias) HIPCHK(hipMemcpyAsync(db, bias, (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
+        else HIPCHK(hipMemsetAsync(db, 0, (size_t)D * 4, c->stream));
+        HIPCHK(hipMemcpyAsync(dk, K, nkv * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dv, V, nkv * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemsetAsync(dout, 0xff, 2 * no * 2, c->stream));
+        HIPCHK(hipMemsetAsync(st, 0, (size_t)rows * sizeof(SelState), c->stream));
+        launch_dec_cross_attn(dq, ks, (legacy && !bias) ? nullptr : db, dk, dv, rows, H, T_ENC, beam, dout, (int64_t)no, ws,
+                              c->xticket, st, c->stream, dmap);
+        hipError_t e = hipGetLastError();
+        // the tickets are zero between launches (the last arriver resets its own); after a
+        // failed launch they may not be, and the decode path shares them
+        hipError_t e2 = hipMemsetAsync(c->xticket, 0, (size_t)W * H * sizeof(int), c->stream);
+        HIPCHK(e);
+        HIPCHK(e2);
+        std::vector<h16> back(2 * no);
+        HIPCHK(hipMemcpyAsync(back.data(), dout, 2 * no * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < no; ++i) out[i] = (float)back[i] + (float)back[no + i];
+    });
+}
+}  // namespace
+
+int osw_debug_dec_xattn(osw_ctx* c, const float* q_slabs, int32_t ks, const float* bias, const void* K, const void* V,
+                        int32_t rows, int32_t beam, int32_t legacy, float* out) {
+    return debug_dec_xattn(c, q_slabs, ks, bias, K, V, beam >= 1 ? rows / beam : 0, nullptr, rows, beam, legacy, out);
+}
+
+int osw_debug_dec_xattn_windows(osw_ctx* c, const float* q_slabs, int32_t ks, const float* bias, const void* K,
+                                const void* V, int32_t kv_windows, const int32_t* window_map, int32_t rows, int32_t beam,
+                                int32_t legacy, float* out) {
+    if (!window_map) return guard([&] { REQUIRE(false, "null window map"); });
+    return debug_dec_xattn(c, q_slabs, ks, bias, K, V, kv_windows, window_map, rows, beam, legacy, out);
+}
+
+int osw_debug_dec_self_attn(osw_ctx* c, const float* qkv_slabs, int32_t ks, const float* bias, void* kcache, void* vcache,
+                            int32_t rows, const int32_t* pos, int32_t pos_per_row, const int32_t* ancestry,
+                            int32_t group, float* out) {
+    return guard([&] {
+        REQUIRE(c && qkv_slabs && bias && kcache && vcache && pos && out, "null argument");
+        REQUIRE(ks >= 1 && ks <= 32, "ks out of range");
+        REQUIRE(rows >= 1 && rows <= 1024, "rows out of range");
+        const int H = c->d.n_text_head, D = c->d.n_text_state, ctx = c->d.n_text_ctx;
+        REQUIRE(ctx >= 1 && ctx <= 448, "n_text_ctx out of range");
+        for (int r = 0; r < (pos_per_row ? rows : 1); ++r) REQUIRE(pos[r] >= 0 && pos[r] < ctx, "position outside the cache");
+        if (ancestry) {
+            REQUIRE(group >= 1 && group <= MAX_BEAM && rows % group == 0, "rows must be windows x group, group <= 8");
+            for (size_t i = 0; i < (size_t)rows * ctx; ++i)
+                REQUIRE(ancestry[i] >= 0 && ancestry[i] < rows, "ancestry names a row outside the cache");
+        } else {
+            REQUIRE(group == 1, "group needs an ancestry table");
+        }
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t nq = (size_t)ks * rows * 3 * D, nkv = (size_t)rows * H * ctx * 64, no = (size_t)rows * D;
+        float* dq = dalloc<float>(nq, tmp.v);
+        float* db = dalloc<float>((size_t)3 * D, tmp.v);
+        h16* dk = dalloc<h16>(nkv, tmp.v);
+        h16* dv = dalloc<h16>(nkv, tmp.v);
+        h16* dout = dalloc<h16>(2 * no, tmp.v);
+        int* dpos = dalloc<int>((size_t)rows, tmp.v);
+        int* danc = ancestry ? dalloc<int>((size_t)rows * ctx, tmp.v) : nullptr;
+        SelState* st = dalloc<SelState>((size_t)rows, tmp.v);
+        HIPCHK(hipMemcpyAsync(dq, qkv_slabs, nq * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(db, bias, (size_t)3 * D * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dk, kcache, nkv * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dv, vcache, nkv * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dpos, pos, (size_t)(pos_per_row ? rows : 1) * 4, hipMemcpyHostToDevice, c->stream));
+        if (danc) HIPCHK(hipMemcpyAsync(danc, ancestry, (size_t)rows * ctx * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemsetAsync(dout, 0xff, 2 * no * 2, c->stream));
+        HIPCHK(hipMemsetAsync(st, 0, (size_t)rows * sizeof(SelState), c->stream));
+        launch_dec_self_attn(dq, ks, db, dk, dv, dpos, rows, H, ctx, dout, (int64_t)no, danc, group, st, c->stream,
+                             pos_per_row ? 1 : 0);
+        HIPCHK(hipGetLastError());
+        std::vector<h16> back(2 * no);
+        HIPCHK(hipMemcpyAsync(back.data(), dout, 2 * no * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(kcache, dk, nkv * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(vcache, dv, nkv * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < no; ++i) out[i] = (float)back[i] + (float)back[no + i];
+    });
+}
+
+namespace {
+// what launch_gemm_skinny_partial / launch_gemm_skinny_pro and gemm_skinny_kernel rely on: whole
+// 128-deep K ranges (the kernel's k32 steps come in fours, its chunk clamps assume kc >= 128)
+void require_skinny_split(int K, int ks) {
+    REQUIRE(K >= 128 && K % 128 == 0, "the skinny GEMM needs K a multiple of 128");
+    REQUIRE(ks >= 1 && K % ks == 0 && (K / ks) % 128 == 0, "the skinny GEMM needs K / ksplit a multiple of 128");
+}
+
+// W[N][K] (host fp16) on the device, with its fragment-major copy when asked for
+struct DebugW {
+    h16* w = nullptr;
+    h16* wf = nullptr;
+};
+void upload_w(osw_ctx* c, const void* W, int N, int K, bool use_wf, TmpBufs& tmp, DebugW& d) {
+    d.w = dalloc<h16>((size_t)N * K, tmp.v);
+    HIPCHK(hipMemcpyAsync(d.w, W, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
+    if (use_wf) {
+        d.wf = dalloc<h16>((size_t)((N + 15) / 16) * 16 * K, tmp.v);
+        launch_frag_pack(d.w, K, N, K, d.wf, c->stream);
+        HIPCHK(hipGetLastError());
+    }
+}
+
+// the fp32 result buffer of a debug call: out_floats floats of 0xff bytes (a NaN pattern), so an
+// element the kernel did not write, and a write past the `need` floats it owns, both show
+float* result_buf(osw_ctx* c, int64_t out_floats, TmpBufs& tmp) {
+    float* d = dalloc<float>((size_t)out_floats, tmp.v);
+    HIPCHK(hipMemsetAsync(d, 0xff, (size_t)out_floats * 4, c->stream));
+    return d;
+}
+}  // namespace
+
+int osw_debug_dec_gemm(osw_ctx* c, int32_t form, int32_t M, int32_t N, int32_t K, const void* A_hi, const void* A_lo,
+                       const void* W, int32_t use_wf, float* out, int64_t out_floats, int32_t* ks_out) {
+    return guard([&] {
+        REQUIRE(c && A_hi && W && out && ks_out, "null argument");
+        REQUIRE(form >= 0 && form <= 2, "form: 0 skinny slabs, 1 tiled slabs, 2 logits route");
+        REQUIRE(M >= 1 && M <= 1024 && N >= 1 && N <= 65536 && K >= 64 && K <= 8192, "GEMM shape out of range");
+        REQUIRE(A_lo || M <= 64, "more than 64 rows need the lo operand (32-row groups)");
+        int ks = 1;
+        bool skinny = true;
+        GemmArgs g = gemm_plain(nullptr, K, nullptr, nullptr, M, N, K, nullptr, N, EPI_F32);
+        if (form == 0) {
+            ks = skinny_ksplit(N, K);
+            require_skinny_split(K, ks);
+        } else if (form == 1) {
+            REQUIRE(A_lo, "the tiled split-K GEMM serves hi/lo decoder rows");
+            REQUIRE(K % 64 == 0 && N % 2 == 0, "the wide kernel needs K % 64 == 0 and an even N (8-byte stores)");
+            ks = tiled_ksplit(M, N, K);
+            REQUIRE(K % ks == 0 && (K / ks) % 64 == 0, "tiled split: K / ksplit a multiple of 64");
+            skinny = false;
+        } else {
+            skinny = skinny_ok(g);  // run_gemm's test (shape and epilogue only)
+            if (skinny) {
+                ks = skinny_ksplit(N, K);
+                require_skinny_split(K, ks);
+            } else {
+                REQUIRE(A_lo, "the logits route beyond the skinny kernel serves hi/lo rows");
+                REQUIRE(K % 64 == 0 && N % 2 == 0, "the wide kernel needs K % 64 == 0 and an even N (8-byte stores)");
+            }
+        }
+        const int64_t need = form == 2 ? (int64_t)M * N : (int64_t)ks * M * N;
+        REQUIRE(out_floats >= need && out_floats <= ((int64_t)1 << 27), "out_floats: the result's floats plus a guard band");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t na = (size_t)M * K;  // lo sits R = M rows after hi, as xdn / dattn / dh hold the pair
+        h16* dA = dalloc<h16>(2 * na, tmp.v);
+        HIPCHK(hipMemcpyAsync(dA, A_hi, na * 2, hipMemcpyHostToDevice, c->stream));
+        if (A_lo) HIPCHK(hipMemcpyAsync(dA + na, A_lo, na * 2, hipMemcpyHostToDevice, c->stream));
+        else HIPCHK(hipMemsetAsync(dA + na, 0, na * 2, c->stream));
+        DebugW dw;
+        upload_w(c, W, N, K, use_wf != 0, tmp, dw);
+        float* dout = result_buf(c, out_floats, tmp);
+        g.A = dA;
+        g.A_lo = A_lo ? dA + na : nullptr;
+        g.W = dw.w;
+        g.Wf = dw.wf;
+        if (form == 0) {
+            const int got = launch_gemm_skinny_partial(g, dout, c->stream);
+            REQUIRE(got == ks, "launch_gemm_skinny_partial chose another split");
+        } else if (form == 1) {
+            launch_gemm_tiled_partial(g, dout, ks, c->stream);
+        } else {
+            // decoder_step's logits GEMM: run_gemm's choice (with a workspace of this call's own)
+            g.C = dout;
+            g.share_cus = c->share_cus;
+            if (skinny) {
+                float* part = dalloc<float>((size_t)ks * M * N, tmp.v);
+                launch_gemm_skinny(g, part, c->stream);
+            } else {
+                launch_gemm(g, c->stream);
+            }
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, dout, (size_t)out_floats * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        *ks_out = ks;
+    });
+}
+
+int osw_debug_dec_resln(osw_ctx* c, int32_t fused, int32_t direct, int32_t rows, int32_t D, const float* slabs,
+                        int32_t ks, const float* bias, float* x, const float* gain, const float* shift,
+                        const void* tok_emb, const float* pos_emb, const int32_t* tok, const int32_t* pos, int32_t ctx,
+                        int32_t V, int32_t pos_row, const void* W, int32_t N, int32_t use_wf, float* x_out, void* y_hi,
+                        void* y_lo, float* out, int64_t out_floats, int32_t* ks_out) {
+    return guard([&] {
+        REQUIRE(c && x && gain && shift && x_out, "null argument");
+        REQUIRE(rows >= 1 && rows <= 64, "rows out of range");
+        REQUIRE(D >= 4 && D % 4 == 0 && D <= 1280, "LayerNorm width: a multiple of 4, at most 1280");
+        const bool embed = slabs == nullptr;
+        if (embed) {
+            REQUIRE(tok_emb && pos_emb && tok && pos, "the embedding entry needs tok_emb, pos_emb, tok and pos");
+            REQUIRE(V >= 1 && V <= 65536 && ctx >= 1 && ctx <= 448, "embedding tables out of range");
+            // (a token id is clamped into [0, V) by the kernel; a position only from above)
+            for (int r = 0; r < (pos_row ? rows : 1); ++r) REQUIRE(pos[r] >= 0, "negative position");
+        } else {
+            REQUIRE(ks >= 1 && ks <= 64, "ks out of range");
+        }
+        int gks = 1;
+        int64_t need = 0;
+        if (fused) {
+            REQUIRE(W && out && ks_out, "null argument");
+            REQUIRE(rows <= PRO_ROWS, "PRO_RESLN serves at most PRO_ROWS rows");
+            REQUIRE(N >= 1 && N <= 65536, "N out of range");
+            gks = direct ? 1 : skinny_ksplit(N, D);
+            require_skinny_split(D, gks);
+            need = (int64_t)gks * rows * N;
+            REQUIRE(out_floats >= need && out_floats <= ((int64_t)1 << 27), "out_floats: the result's floats plus a guard band");
+        } else {
+            REQUIRE(y_hi && y_lo, "null argument");
+        }
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t nx = (size_t)rows * D;
+        float* dx = dalloc<float>(nx, tmp.v);
+        float* dg = dalloc<float>(D, tmp.v);
+        float* db = dalloc<float>(D, tmp.v);
+        float* dbias = bias ? dalloc<float>(D, tmp.v) : nullptr;
+        float* dpart = nullptr;
+        h16* dte = nullptr;
+        float* dpe = nullptr;
+        int *dtok = nullptr, *dpos = nullptr;
+        HIPCHK(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dg, gain, (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(db, shift, (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
+        if (bias) HIPCHK(hipMemcpyAsync(dbias, bias, (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
+        if (embed) {
+            dte = dalloc<h16>((size_t)V * D, tmp.v);
+            dpe = dalloc<float>((size_t)ctx * D, tmp.v);
+            dtok = dalloc<int>((size_t)rows, tmp.v);
+            dpos = dalloc<int>((size_t)rows, tmp.v);
+            HIPCHK(hipMemcpyAsync(dte, tok_emb, (size_t)V * D * 2, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(dpe, pos_emb, (size_t)ctx * D * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(dtok, tok, (size_t)rows * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(dpos, pos, (size_t)(pos_row ? rows : 1) * 4, hipMemcpyHostToDevice, c->stream));
+        } else {
+            dpart = dalloc<float>((size_t)ks * nx, tmp.v);
+            HIPCHK(hipMemcpyAsync(dpart, slabs, (size_t)ks * nx * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        if (!fused) {
+            h16* dy = dalloc<h16>(2 * nx, tmp.v);  // hi, then lo
+            HIPCHK(hipMemsetAsync(dy, 0xff, 2 * nx * 2, c->stream));
+            launch_dec_resid_ln(dpart, ks, rows, D, dbias, dx, dg, db, dy, (int64_t)nx, dte, dpe, dtok, dpos, ctx, V,
+                                c->stream, pos_row ? 1 : 0);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(x_out, dx, nx * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(y_hi, dy, nx * 2, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(y_lo, dy + nx, nx * 2, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            return;
+        }
+        // the fused step's ping-pong: every workgroup reads x, one writes x' to the other buffer
+        float* dx2 = dalloc<float>(nx, tmp.v);
+        HIPCHK(hipMemsetAsync(dx2, 0xff, nx * 4, c->stream));
+        DebugW dw;
+        upload_w(c, W, N, D, use_wf != 0, tmp, dw);
+        float* dout = result_buf(c, out_floats, tmp);
+        GemmArgs g = gemm_plain(nullptr, D, dw.w, nullptr, rows, N, D, direct ? dout : nullptr, direct ? N : 0, EPI_F32);
+        g.Wf = dw.wf;
+        ProArgs pa{};
+        pa.ln = ResLnArgs{dpart, ks, (int64_t)nx, dbias, dx, dx2, dg, db, dte, dpe, dtok, dpos, ctx, D, V, pos_row ? 1 : 0};
+        const int got = launch_gemm_skinny_pro(g, PRO_RESLN, pa, direct != 0, direct ? nullptr : dout, c->stream);
+        HIPCHK(hipGetLastError());
+        REQUIRE(got == gks, "launch_gemm_skinny_pro chose another split");
+        HIPCHK(hipMemcpyAsync(x_out, dx2, nx * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(x, dx, nx * 4, hipMemcpyDeviceToHost, c->stream));  // must come back unchanged
+        HIPCHK(hipMemcpyAsync(out, dout, (size_t)out_floats * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        *ks_out = gks;
+    });
+}
+
+int osw_debug_dec_gelu(osw_ctx* c, int32_t fused, int32_t M, int32_t K4, const float* slabs, int32_t ks,
+                       const float* bias, const void* W, int32_t N, int32_t use_wf, void* y_hi, void* y_lo, float* out,
+                       int64_t out_floats, int32_t* ks_out) {
+    return guard([&] {
+        REQUIRE(c && slabs && bias, "null argument");
+        REQUIRE(M >= 1 && M <= 1024 && K4 >= 1 && K4 <= 8192, "shape out of range");
+        REQUIRE(ks >= 1 && ks <= 64, "ks out of range");
+        int gks = 1;
+        int64_t need = 0;
+        if (fused) {
+            REQUIRE(W && out && ks_out, "null argument");
+            REQUIRE(N >= 1 && N <= 65536, "N out of range");
+            REQUIRE(M <= GELU_ROWS, "PRO_GELU serves at most GELU_ROWS rows");
+            REQUIRE(K4 >= 128 && K4 % 128 == 0, "the skinny GEMM needs K a multiple of 128");
+            gks = skinny_ksplit(N, K4);
+            require_skinny_split(K4, gks);
+            REQUIRE(K4 / gks <= GELU_KC, "PRO_GELU: a workgroup's K range is at most GELU_KC deep");
+            need = (int64_t)gks * M * N;
+            REQUIRE(out_floats >= need && out_floats <= ((int64_t)1 << 27), "out_floats: the result's floats plus a guard band");
+        } else {
+            REQUIRE(y_hi && y_lo, "null argument");
+        }
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t n = (size_t)M * K4;
+        float* dpart = dalloc<float>((size_t)ks * n, tmp.v);
+        float* dbias = dalloc<float>(K4, tmp.v);
+        HIPCHK(hipMemcpyAsync(dpart, slabs, (size_t)ks * n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dbias, bias, (size_t)K4 * 4, hipMemcpyHostToDevice, c->stream));
+        if (!fused) {
+            h16* dy = dalloc<h16>(2 * n, tmp.v);  // hi, then lo
+            HIPCHK(hipMemsetAsync(dy, 0xff, 2 * n * 2, c->stream));
+            launch_dec_reduce_gelu(dpart, ks, M, K4, dbias, dy, (int64_t)n, c->stream);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(y_hi, dy, n * 2, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(y_lo, dy + n, n * 2, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            return;
+        }
+        DebugW dw;
+        upload_w(c, W, N, K4, use_wf != 0, tmp, dw);
+        float* dout = result_buf(c, out_floats, tmp);
+        GemmArgs g = gemm_plain(nullptr, K4, dw.w, nullptr, M, N, K4, nullptr, 0, EPI_F32);
+        g.Wf = dw.wf;
+        ProArgs pg{};
+        pg.part = dpart;
+        pg.ks = ks;
+        pg.bias = dbias;
+        const int got = launch_gemm_skinny_pro(g, PRO_GELU, pg, false, dout, c->stream);
+        HIPCHK(hipGetLastError());
+        REQUIRE(got == gks, "launch_gemm_skinny_pro chose another split");
+        HIPCHK(hipMemcpyAsync(out, dout, (size_t)out_floats * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        *ks_out = gks;
+    });
+}
+
+namespace {
+// one past the farthest element that rows 0 .. M-1 of a grouped layout touch, each row `width`
+// elements wide (row m at (m / grp_rows) * grp_stride + (m % grp_rows) * ld): the last row of
+// every group is a candidate (a short last group may end before the one in front of it)
+int64_t grouped_extent(int64_t M, int64_t grp_rows, int64_t grp_stride, int64_t ld, int64_t width) {
+    int64_t end = 0;
+    for (int64_t q = 0; q * grp_rows < M; ++q) {
+        const int64_t rows = std::min(grp_rows, M - q * grp_rows);
+        end = std::max(end, q * grp_stride + (rows - 1) * ld + width);
+    }
+    return end;
+}
+}  // namespace
+
+int osw_debug_enc_gemm(osw_ctx* c, const osw_enc_gemm_desc* d) {
+    return guard([&] {
+        REQUIRE(c && d && d->A && d->W && d->C, "null argument");
+        const int M = d->M, N = d->N, K = d->K, epi = d->epi, variant = d->variant;
+        REQUIRE(M >= 1 && M <= 65536 && N >= 1 && N <= 8192 && K >= 64 && K <= 8192, "GEMM shape out of range");
+        REQUIRE(K % 64 == 0, "GEMM K must be a multiple of 64");
+        REQUIRE(epi >= EPI_F16 && epi <= EPI_HEADS, "epi: one of the six OSW_EPI_* epilogues");
+        REQUIRE(variant == 0 || variant == 1 || variant == 2 || variant == 4 || variant == 6 || variant == 7 ||
+                    variant == 11 || variant == 16,
+                "variant: 0 (chooser), 1, 2, 4, 6, 7, 11 or 16");
+        // A: 16-B pieces (global_load_lds), every row's K elements inside the buffer
+        REQUIRE(d->lda >= 0 && d->lda <= ((int64_t)1 << 24) && d->lda % 8 == 0, "lda: a multiple of 8 elements (16 B)");
+        REQUIRE(d->a_grp_rows >= 1 && d->a_grp_rows <= M, "a_grp_rows out of range");
+        REQUIRE(d->a_grp_stride >= 0 && d->a_grp_stride <= ((int64_t)1 << 31) && d->a_grp_stride % 8 == 0,
+                "a_grp_stride: a multiple of 8 elements (16 B)");
+        REQUIRE(d->a_count >= 1 && d->a_count <= ((int64_t)1 << 28), "a_count out of range");
+        REQUIRE(grouped_extent(M, d->a_grp_rows, d->a_grp_stride, d->lda, K) <= d->a_count,
+                "an A row reads past the A buffer");
+        // C
+        const bool heads = epi == EPI_HEADS;
+        const bool f32 = epi == EPI_F32_RESID || epi == EPI_F32_GELU_POS || epi == EPI_F32;
+        const int64_t esz = f32 ? 4 : 2;
+        REQUIRE(d->c_bytes >= esz && d->c_bytes <= ((int64_t)1 << 30) && d->c_bytes % esz == 0, "c_bytes out of range");
+        const int64_t c_count = d->c_bytes / esz;
+        REQUIRE(d->c_offset >= 0 && d->c_offset < c_count, "c_offset outside the C buffer");
+        REQUIRE(d->ldc >= 0 && d->ldc <= ((int64_t)1 << 24), "ldc out of range");
+        REQUIRE(d->c_grp_rows >= 1 && d->c_grp_rows <= M, "c_grp_rows out of range");
+        REQUIRE(d->c_grp_stride >= 0 && d->c_grp_stride <= ((int64_t)1 << 31), "c_grp_stride out of range");
+        if (f32) {
+            // f32x4 accesses of the staged fp32 epilogues (bias, residual, positional rows, stores);
+            // the plain fp32 store too, which the 256-row tiles stage the same way
+            REQUIRE(N % 4 == 0 && d->ldc % 4 == 0 && d->c_grp_stride % 4 == 0 && d->c_offset % 4 == 0,
+                    "fp32 epilogues need N, ldc, the C group stride and the C offset to be multiples of 4 (16-B rows)");
+            // the two fused fp32 epilogues as run_gemm serves them (the chooser's kernel depends on it)
+            REQUIRE(epi == EPI_F32 || (N % 8 == 0 && d->ldc % 8 == 0 && d->c_grp_stride % 8 == 0),
+                    "GEMM epilogue needs N, ldc and the C group stride to be multiples of 8");
+        } else {
+            // run_gemm's rule: 16-B chunks, only each chunk's first column is tested against N
+            REQUIRE(N % 8 == 0 && d->c_offset % 8 == 0 && (heads || (d->ldc % 8 == 0 && d->c_grp_stride % 8 == 0)),
+                    "GEMM epilogue needs N, ldc, the C group stride and the C offset to be multiples of 8");
+        }
+        int nwin = 0;
+        if (heads) {
+            REQUIRE(d->heads_T >= 1 && d->heads_H >= 1 && d->heads_H <= 64 && d->heads_nb >= 1 && d->heads_nb <= 1024,
+                    "head-major geometry out of range");
+            REQUIRE(N % (64 * d->heads_H) == 0, "EPI_HEADS needs N a multiple of 64 * heads_H");
+            REQUIRE(M % d->heads_T == 0, "EPI_HEADS needs M = windows * heads_T");
+            nwin = M / d->heads_T;
+            if (d->heads_slot) {
+                std::vector<char> seen(d->heads_nb, 0);
+                for (int i = 0; i < nwin; ++i) {
+                    const int sl = d->heads_slot[i];
+                    REQUIRE(sl >= 0 && sl < d->heads_nb && !seen[sl], "heads_slot: distinct slots < heads_nb");
+                    seen[sl] = 1;
+                }
+            } else {
+                REQUIRE(nwin <= d->heads_nb, "more windows than heads_nb");
+            }
+            const int64_t extent = (int64_t)(N / (64 * d->heads_H)) * d->heads_nb * d->heads_H * d->heads_T * 64;
+            REQUIRE(d->c_offset + extent <= c_count, "the head-major output does not fit the C buffer");
+        } else {
+            // rows and groups do not overlap in C (in-bounds stores that race; EPI_F32_RESID reads them too)
+            REQUIRE(d->ldc >= N || M == 1, "ldc shorter than a row");
+            REQUIRE(M <= d->c_grp_rows || d->c_grp_stride >= d->c_grp_rows * d->ldc, "C groups overlap");
+            REQUIRE(d->c_offset + grouped_extent(M, d->c_grp_rows, d->c_grp_stride, d->ldc, N) <= c_count,
+                    "a C row ends past the C buffer");
+        }
+        if (epi == EPI_F32_GELU_POS)
+            REQUIRE(d->pos && d->pos_count == d->c_grp_rows * (int64_t)N, "EPI_F32_GELU_POS needs pos [c_grp_rows][N]");
+        // an explicit variant must run the kernel it names (launch_gemm_variant falls through otherwise)
+        if (variant == 11)
+            REQUIRE(N % 8 == 0 && (heads || d->ldc % 8 == 0) && d->c_grp_stride % 8 == 0,
+                    "the 128 ring needs N, ldc and the C group stride to be multiples of 8");
+        if (variant == 16) REQUIRE(N % 8 == 0, "the half-width tile needs N % 8 == 0");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        h16* dA = dalloc<h16>((size_t)d->a_count, tmp.v);
+        h16* dW = dalloc<h16>((size_t)N * K, tmp.v);
+        char* dC = dalloc<char>((size_t)d->c_bytes, tmp.v);
+        float* dbias = d->bias ? dalloc<float>((size_t)N, tmp.v) : nullptr;
+        float* dpos = epi == EPI_F32_GELU_POS ? dalloc<float>((size_t)d->pos_count, tmp.v) : nullptr;
+        int* dslot = heads && d->heads_slot ? dalloc<int>((size_t)nwin, tmp.v) : nullptr;
+        HIPCHK(hipMemcpyAsync(dA, d->A, (size_t)d->a_count * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dW, d->W, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dC, d->C, (size_t)d->c_bytes, hipMemcpyHostToDevice, c->stream));
+        if (dbias) HIPCHK(hipMemcpyAsync(dbias, d->bias, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+        if (dpos) HIPCHK(hipMemcpyAsync(dpos, d->pos, (size_t)d->pos_count * 4, hipMemcpyHostToDevice, c->stream));
+        if (dslot) HIPCHK(hipMemcpyAsync(dslot, d->heads_slot, (size_t)nwin * 4, hipMemcpyHostToDevice, c->stream));
+        GemmArgs g{};
+        g.A = dA; g.lda = d->lda; g.a_grp_rows = d->a_grp_rows; g.a_grp_stride = d->a_grp_stride;
+        g.W = dW; g.ldw = K; g.bias = dbias; g.M = M; g.N = N; g.K = K;
+        g.C = dC + d->c_offset * esz; g.ldc = d->ldc; g.c_grp_rows = d->c_grp_rows; g.c_grp_stride = d->c_grp_stride;
+        g.pos = dpos; g.epi = epi;
+        g.heads_T = d->heads_T; g.heads_H = d->heads_H; g.heads_nb = d->heads_nb; g.heads_slot = dslot;
+        g.share_cus = c->share_cus;
+        launch_gemm_variant(g, variant, c->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(d->C, dC, (size_t)d->c_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
+int osw_debug_enc_layernorm(osw_ctx* c, int32_t M, int32_t M_alloc, int32_t D, const float* x, const float* gain,
+                            const float* shift, void* y) {
+    return guard([&] {
+        REQUIRE(c && x && gain && shift && y, "null argument");
+        REQUIRE(M >= 1 && M <= M_alloc && M_alloc <= 65536, "rows: 1 <= M <= M_alloc <= 65536");
+        REQUIRE(layernorm_width_ok(D), "no LayerNorm kernel for this width");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        float* dx = dalloc<float>((size_t)M * D, tmp.v);
+        float* dg = dalloc<float>((size_t)D, tmp.v);
+        float* db = dalloc<float>((size_t)D, tmp.v);
+        h16* dy = dalloc<h16>((size_t)M_alloc * D, tmp.v);
+        HIPCHK(hipMemcpyAsync(dx, x, (size_t)M * D * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dg, gain, (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(db, shift, (size_t)D * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dy, y, (size_t)M_alloc * D * 2, hipMemcpyHostToDevice, c->stream));
+        launch_layernorm(dx, M, D, dg, db, dy, c->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(y, dy, (size_t)M_alloc * D * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
+int osw_debug_hold_capture(osw_ctx* c, int32_t hold_ms) {
+    return guard([&] {
+        REQUIRE(c, "null ctx");
+        REQUIRE(hold_ms >= 0 && hold_ms <= 10000, "hold_ms out of range");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        // exactly the locks decode_graph holds around a capture
+        std::unique_lock<std::mutex> no_encoder;
+        if (c->baton) no_encoder = std::unique_lock<std::mutex>(c->baton->mu);
+        GateLock gate_(capture_gate());
+        HIPCHK(hipStreamSynchronize(c->stream));
+        hipGraph_t gr = nullptr;
+        c->capturing = true;
+        try {
+            HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+            HIPCHK(hipMemsetAsync(c->done, 0, sizeof(int), c->stream));  // one captured node
+            const auto t0 = std::chrono::steady_clock::now();
+            while (std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(hold_ms)) {
+                std::this_thread::sleep_for(std::chrono::milliseconds(1));
+                hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+                HIPCHK(hipStreamIsCapturing(c->stream, &st));
+                REQUIRE(st == hipStreamCaptureStatusActive, "the capture was invalidated while held");
+            }
+            HIPCHK(hipStreamEndCapture(c->stream, &gr));
+        } catch (...) {
+            c->capturing = false;
+            hipGraph_t junk = nullptr;
+            (void)hipStreamEndCapture(c->stream, &junk);
+            if (junk) (void)hipGraphDestroy(junk);
+            (void)hipGetLastError();
+            throw;
+        }
+        c->capturing = false;
+        REQUIRE(gr != nullptr, "empty capture");
+        hipGraphExec_t ge = nullptr;
+        hipError_t e = hipGraphInstantiate(&ge, gr, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(gr);
+        HIPCHK(e);
+        (void)hipGraphExecDestroy(ge);
+    });
+}
+
+}  // extern "C"

@@ -639,7 +639,7 @@ struct BeamCand {
 constexpr int BEAM_SLICES = SEL_SPLIT;  // vocabulary slices per row (one pass: the select slices)
 constexpr int TOPK_VPT = 16;            // logits one thread holds
 constexpr int MAXK2 = 2 * MAX_BEAM;
-static_assert(BEAM_SLICES * 256 * TOPK_VPT >= SEL_SPLIT * 4096, "osw.hip admits V <= SEL_SPLIT * 4096: one batch per slice");
+static_assert(BEAM_SLICES * 256 * TOPK_VPT >= SEL_SPLIT * 4096, "plan.h admits V <= SEL_SPLIT * 4096: one batch per slice");
 
 // Ordered keys for the candidate ranking.  score_key: a float as an int with the same
 // order (-0 as +0, NaN excluded by the callers); an involution, so score_of reads the float
@@ -1403,7 +1403,7 @@ __global__ __launch_bounds__(256) void beam_update_kernel(SelParams P, int* __re
     }
 }
 
-// Row refill (osw.hip decode_refill): reset the decoder rows of newly admitted windows.
+// Row refill (decode_host.hip decode_refill): reset the decoder rows of newly admitted windows.
 // pack[i] = {row, token budget, prompt[0 .. P)}; one workgroup per admitted window.
 __global__ __launch_bounds__(64) void refill_rows_kernel(const int* __restrict__ pack, int P, int* __restrict__ prompt,
                                                          int* __restrict__ budget, int* __restrict__ cur_tok,
@@ -1419,7 +1419,7 @@ __global__ __launch_bounds__(64) void refill_rows_kernel(const int* __restrict__
     }
 }
 
-// Decode sessions (osw.hip, osw_session_*): reset the `group` rows of each admitted window
+// Decode sessions (session.hip, osw_session_*): reset the `group` rows of each admitted window
 // slot.  pack[i] = {slot, plen, budget, prompt[0 .. plen)} with stride `ps`; grid (windows,
 // group), 64 threads.  Beam rows (anc != nullptr) also get an identity ancestry and the
 // window's hypothesis bookkeeping a fresh start.
@@ -1485,7 +1485,7 @@ void launch_dec_self_attn(const float* part, int ks, const float* bias, h16* kc,
         const char* e = std::getenv("OSW_SELF_KALL");
         return e ? atoi(e) : 0;
     }();
-    if (anc) {  // ctx <= 448 (osw.hip checks the context at decode)
+    if (anc) {  // ctx <= 448 (osw_create checks the context)
         if (vlate)
             dec_self_attn_kernel<true, false><<<H * B, 256, 0, s>>>(part, ks, bias, kc, vc, pos, H, B, ctx, out, lo_off,
                                                                     anc, group, st, pos_row);

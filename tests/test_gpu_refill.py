@@ -1,4 +1,4 @@
-"""Row refill (osw_transcribe_refill, osw.hip decode_refill): more clips than decoder rows,
+"""Row refill (osw_transcribe_refill, csrc/decode_host.hip decode_refill): more clips than decoder rows,
 every row on its own step counter, a finished window's row refilled with the next queued
 clip's window (encoded straight into that row's cross-K/V slot).  Rows are independent in
 every kernel, so each clip must decode exactly as in a plain osw_transcribe_batch call:

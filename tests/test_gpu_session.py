@@ -1,4 +1,4 @@
-"""Decode sessions (osw_session_*, osw.hip session_step): windows of different clips, seeks,
+"""Decode sessions (osw_session_*, csrc/session.hip session_step): windows of different clips, seeks,
 prefixes and languages admitted into free decoder slots between chunks of decoder steps,
 each slot's rows on their own step counter.  Every row's arithmetic is the plain decode's
 (rows are independent in every kernel), so each window must decode exactly as it does
