@@ -44,6 +44,9 @@
  *   osw_debug_enc_gemm / osw_debug_enc_layernorm
  *       one launch of the encoder's tiled GEMM (any epilogue, grouped rows, head-major scatter)
  *       and of its LayerNorm on host data, used only by the parity tests
+ *   osw_debug_get_logmel / osw_debug_mel_windows
+ *       the front end's raw log10 mel with its clip maximum, and the window-packing kernel
+ *       alone (the conv stem's fp16 operand), used only by the parity tests
  *   osw_decode_opts::repetition_penalty / no_repeat_ngram_size (+ osw_debug_history_rules)
  *       replace   WhisperModel.transcribe(..., repetition_penalty=, no_repeat_ngram_size=):
  *                 ctranslate2's RepetitionPenalty / NoRepeatNgram logits processors [upstream],
@@ -580,6 +583,18 @@ int osw_debug_enc_gemm(osw_ctx* ctx, const osw_enc_gemm_desc* desc);
  * OSW_EINVAL for a width launch_layernorm has no kernel for. */
 int osw_debug_enc_layernorm(osw_ctx* ctx, int32_t M, int32_t M_alloc, int32_t D, const float* x, const float* gain,
                             const float* shift, void* y);
+
+/* ---- the log-mel front end's intermediate values (parity tests: tests/test_gpu_mel.py) ----
+ * The raw fp32 log10 mel of clip `clip` of the last osw_log_mel, time-major [n_frames][n_mels], as
+ * mel_logmel_kernel stored it (before the max - 8 clamp and the (x + 4) / 4 scaling of osw_get_mel),
+ * and in *clip_max the clip's maximum as the kernels read it (decoded from its ordered-int form). */
+int osw_debug_get_logmel(osw_ctx* ctx, int32_t clip, float* out, int64_t out_floats, float* clip_max);
+/* mel_window_kernel alone on n <= max_batch windows of the resident log-mel: the windows are checked
+ * as osw_encode_windows checks them (OSW_EINVAL with the same message, before any launch), then
+ * out_halfs receives the conv stem's operand X1 [n][3002][C1] as fp16 bits, C1 = n_mels rounded up
+ * to a multiple of 64: row 1 + t is frame seek + t, normalised; rows 0 and 3001, rows past the
+ * segment and columns past n_mels are zero.  out_count: the buffer's size in fp16 elements. */
+int osw_debug_mel_windows(osw_ctx* ctx, const osw_window* windows, int32_t n, void* out_halfs, int64_t out_count);
 
 /* Test hook for the concurrency contract: holds a stream capture open on the context's
  * stream for hold_ms (under the same locks as a decode-graph capture) and fails if it was

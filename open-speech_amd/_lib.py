@@ -159,6 +159,9 @@ _SIGS = {
     "osw_debug_enc_gemm": (C.c_int, [C.c_void_p, P(osw_enc_gemm_desc)]),
     "osw_debug_enc_layernorm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float),
                                           P(C.c_float), C.c_void_p]),
+    # the log-mel front end's raw values and its window-packing kernel alone (parity tests)
+    "osw_debug_get_logmel": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), C.c_int64, P(C.c_float)]),
+    "osw_debug_mel_windows": (C.c_int, [C.c_void_p, P(osw_window), C.c_int32, C.c_void_p, C.c_int64]),
     "osw_debug_hold_capture": (C.c_int, [C.c_void_p, C.c_int32]),
     "osw_set_encoder_baton_min": (C.c_int, [C.c_void_p, C.c_int32]),
     "osw_set_profiling": (C.c_int, [C.c_void_p, C.c_int32]),

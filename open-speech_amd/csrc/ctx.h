@@ -377,6 +377,7 @@ GemmArgs gemm_plain(const h16* A, int64_t lda, const h16* Wt, const float* bias,
 bool skinny_ok(const GemmArgs& g);
 void run_gemm(osw_ctx* c, const GemmArgs& g0, int cls);
 void encoder_layer(osw_ctx* c, int i, int nb);
+std::vector<int> pack_windows(osw_ctx* c, const osw_window* wins, int n);
 void encode(osw_ctx* c, const osw_window* wins, int n, const int* slots = nullptr);
 void reserve_clips(osw_ctx* c, int n);
 

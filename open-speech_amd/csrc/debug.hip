@@ -766,6 +766,43 @@ int osw_debug_enc_layernorm(osw_ctx* c, int32_t M, int32_t M_alloc, int32_t D, c
     });
 }
 
+int osw_debug_get_logmel(osw_ctx* c, int32_t clip, float* out, int64_t out_floats, float* clip_max) {
+    return guard([&] {
+        REQUIRE(c && out && clip_max, "null argument");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        REQUIRE(clip >= 0 && clip < c->n_clips, "clip out of range");
+        const int64_t n = (int64_t)c->nframes[clip] * c->d.n_mels;
+        REQUIRE(out_floats >= n, "output buffer too small");
+        int32_t ordered = 0;
+        HIPCHK(hipMemcpyAsync(out, c->logmel + c->mel_off[clip], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(&ordered, c->clip_max + clip, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        // float_to_ordered's inverse (common.h), on the host
+        const int32_t bits = ordered >= 0 ? ordered : (ordered ^ 0x7fffffff);
+        std::memcpy(clip_max, &bits, 4);
+    });
+}
+
+int osw_debug_mel_windows(osw_ctx* c, const osw_window* windows, int32_t n, void* out_halfs, int64_t out_count) {
+    return guard([&] {
+        REQUIRE(c && windows && out_halfs, "null argument");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        REQUIRE(!c->sess, "a decode session is open on this context (osw_session_end first)");
+        REQUIRE(n >= 1 && n <= c->B, "window count out of range");
+        const int64_t need = (int64_t)n * 3002 * c->C1;
+        REQUIRE(out_count >= need, "output buffer too small");
+        const std::vector<int> hw = pack_windows(c, windows, n);  // a refused window: no launch
+        HIPCHK(hipMemcpyAsync(c->win, hw.data(), hw.size() * 4, hipMemcpyHostToDevice, c->stream));
+        launch_mel_window(c->logmel, c->mel_off_d, c->nframes_d, c->clip_max, c->win, c->win + n, c->win + 2 * n, n,
+                          c->d.n_mels, c->C1, c->X1, c->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out_halfs, c->X1, (size_t)need * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
 int osw_debug_hold_capture(osw_ctx* c, int32_t hold_ms) {
     return guard([&] {
         REQUIRE(c, "null ctx");

@@ -147,7 +147,9 @@ __global__ __launch_bounds__(256) void mel_logmel_kernel(
         for (int j = 0; j < FPB / 2; ++j) {
             const int t = t0 + f0 + j;
             if (t >= nf) break;
-            const float lg = log10f(fmaxf(s[j], 1e-10f));
+            // a clamped element is -10 by definition, and nothing lies below it: log10f(1e-10f)
+            // is -10.000001 here (one ulp off), which a silent clip had as its maximum
+            const float lg = fmaxf(log10f(fmaxf(s[j], 1e-10f)), -10.0f);
             logmel[mel_off[clip] + (int64_t)t * n_mels + m] = lg;
             lmax = fmaxf(lmax, lg);
         }

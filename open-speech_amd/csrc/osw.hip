@@ -396,6 +396,22 @@ void encoder_layer(osw_ctx* c, int i, int nb) {
                            EPI_F32_RESID), CL_ENC_GEMM);
 }
 
+// The windows of one launch_mel_window, checked against the resident clips: clip, seek and size
+// (trimmed to a window's N_FR frames) as the kernel's three int arrays, [3][n].  encode() and
+// osw_debug_mel_windows both take their windows through here.
+std::vector<int> pack_windows(osw_ctx* c, const osw_window* wins, int n) {
+    std::vector<int> hw(3 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+        REQUIRE(wins[i].clip >= 0 && wins[i].clip < c->n_clips, "window clip out of range");
+        REQUIRE(wins[i].seek >= 0 && wins[i].seek < c->nframes[wins[i].clip], "window seek out of range");
+        REQUIRE(wins[i].segment_size >= 1, "empty window");
+        hw[i] = wins[i].clip;
+        hw[n + i] = wins[i].seek;
+        hw[2 * n + i] = std::min(wins[i].segment_size, N_FR);
+    }
+    return hw;
+}
+
 // slots (row refill): window i's cross K/V goes to decoder row slots[i] of a c->B-row layout
 void encode(osw_ctx* c, const osw_window* wins, int n, const int* slots) {
     REQUIRE(c->finalized, "weights not finalized");
@@ -409,15 +425,7 @@ void encode(osw_ctx* c, const osw_window* wins, int n, const int* slots) {
             seen[slots[i]] = 1;
         }
     }
-    std::vector<int> hw(3 * n);
-    for (int i = 0; i < n; ++i) {
-        REQUIRE(wins[i].clip >= 0 && wins[i].clip < c->n_clips, "window clip out of range");
-        REQUIRE(wins[i].seek >= 0 && wins[i].seek < c->nframes[wins[i].clip], "window seek out of range");
-        REQUIRE(wins[i].segment_size >= 1, "empty window");
-        hw[i] = wins[i].clip;
-        hw[n + i] = wins[i].seek;
-        hw[2 * n + i] = std::min(wins[i].segment_size, N_FR);
-    }
+    const std::vector<int> hw = pack_windows(c, wins, n);
     HIPCHK(hipMemcpyAsync(c->win, hw.data(), hw.size() * 4, hipMemcpyHostToDevice, c->stream));
     std::unique_lock<std::mutex> baton;  // held while this encoder is enqueued (EncBaton)
     // Encoders of fewer than c->baton_min (9) windows skip the baton: a streaming call's

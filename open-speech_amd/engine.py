@@ -823,6 +823,25 @@ class WhisperEngine:
                                                     out.ctypes.data_as(C.c_void_p)), "osw_debug_enc_layernorm")
         return out
 
+    def debug_get_logmel(self, clip: int) -> tuple[np.ndarray, np.float32]:
+        """The raw fp32 log10 mel of a clip of the last log_mel, time-major [n_frames][n_mels], as the
+        kernel stored it, and the clip's maximum as the kernels read it (osw_debug_get_logmel)."""
+        out = np.empty((self._nframes[clip], self.dims.n_mels), np.float32)
+        mx = C.c_float()
+        _lib.check(self.lib.osw_debug_get_logmel(self.ctx, int(clip), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                                 out.size, C.byref(mx)), "osw_debug_get_logmel")
+        return out, np.float32(mx.value)
+
+    def debug_mel_windows(self, windows: list) -> np.ndarray:
+        """mel_window_kernel alone on (clip, seek, segment_size) windows of the resident log-mel
+        (osw_debug_mel_windows): the conv stem's operand X1 as fp16 [n][3002][C1]."""
+        arr = (_lib.osw_window * len(windows))(*[_lib.osw_window(int(c), int(s), int(z)) for c, s, z in windows])
+        c1 = (self.dims.n_mels + 63) // 64 * 64
+        out = np.empty((len(windows), 3002, c1), np.float16)
+        _lib.check(self.lib.osw_debug_mel_windows(self.ctx, arr, len(windows), out.ctypes.data_as(C.c_void_p),
+                                                  out.size), "osw_debug_mel_windows")
+        return out
+
     def hold_capture(self, hold_ms: int) -> None:
         """Test hook (osw_debug_hold_capture): hold a stream capture open on this context's
         stream for ``hold_ms`` under the decode-graph capture's locks; raises if the
