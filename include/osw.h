@@ -115,13 +115,23 @@ extern "C" {
 
 typedef struct osw_ctx osw_ctx;
 
+/* n_audio_ctx is the encoder window: T = 50 * chunk_length positions for faster-whisper's
+ * transcribe(chunk_length = 1..30 whole seconds), i.e. one of 50, 100, ..., 1500 (1500 = Whisper's own
+ * 30 s window, the default everywhere).  osw_create returns OSW_EINVAL for any other value before it
+ * allocates.  A context's window is fixed: every buffer is sized for it (X1 [w][2T + 2][C1], H1
+ * [w][2T + 1][D], the residual / QKV / FC1 rows w * T, cross-K/V [L * 2][w][H][T][64]), "enc.pos" is a
+ * [T][D] tensor (the first T rows of a checkpoint's table), a window holds at most 2T mel frames, and
+ * sibling contexts share it.  The semantics (segment_size = min(100 * chunk_length, content_frames -
+ * seek), zero padding to 100 * chunk_length frames, timestamp rules and the 448-position decoder
+ * unchanged) restate upstream faster-whisper and are not pinned against it. */
 typedef struct osw_dims {
     int32_t n_mels, n_audio_ctx, n_audio_state, n_audio_head, n_audio_layer;
     int32_t n_vocab, n_text_ctx, n_text_state, n_text_head, n_text_layer;
 } osw_dims;
 
-/* One 30 s decoding window: frames [seek, seek + segment_size) of clip `clip`'s
- * log-mel, zero padded to 3000 frames (faster-whisper pad_or_trim). */
+/* One decoding window (30 s unless the context was created with a shorter n_audio_ctx): frames
+ * [seek, seek + segment_size) of clip `clip`'s log-mel, zero padded to 2 * n_audio_ctx frames (3000;
+ * faster-whisper pad_or_trim); a larger segment_size is trimmed to that. */
 typedef struct osw_window {
     int32_t clip;
     int32_t seek;
@@ -257,7 +267,7 @@ int osw_get_mel(osw_ctx* ctx, int32_t clip, float* out, int64_t out_floats);  /*
 
 /* Encoder + cross-attention K/V for n windows of the resident log-mel. */
 int osw_encode_windows(osw_ctx* ctx, const osw_window* windows, int32_t n);
-int osw_get_encoder_output(osw_ctx* ctx, int32_t window, float* out, int64_t out_floats); /* [1500][D] */
+int osw_get_encoder_output(osw_ctx* ctx, int32_t window, float* out, int64_t out_floats); /* [n_audio_ctx][D] */
 
 /* Decode of the n windows last encoded, per `opts`: greedy (beam_size <= 1,
  * temperature <= 0), CTranslate2-style beam search (beam_size > 1; the reference calls
@@ -280,7 +290,7 @@ int osw_decode_window_list(osw_ctx* ctx, int32_t n, const int32_t* windows, cons
                            osw_window_result* res);
 
 /* mel + encode + decode (greedy, beam search or sampling per `opts`, as
- * osw_decode_windows) of window 0 (seek 0, min(frames, 3000)) of every clip. */
+ * osw_decode_windows) of window 0 (seek 0, min(frames, 2 * n_audio_ctx)) of every clip. */
 int osw_transcribe_batch(osw_ctx* ctx, const int16_t* pcm, const int64_t* offsets, int32_t n_clips,
                          int32_t pcm_on_device, const osw_decode_opts* opts, osw_window_result* res);
 
@@ -313,7 +323,7 @@ int osw_transcribe_refill(osw_ctx* ctx, const int16_t* pcm, const int64_t* offse
 typedef struct osw_session_window {
     int64_t tag;              /* the caller's id, returned with the result */
     int32_t seek;             /* first mel frame of the window in its clip */
-    int32_t segment_size;     /* frames (<= 3000) */
+    int32_t segment_size;     /* frames (<= 2 * n_audio_ctx) */
     int32_t language_token;   /* -1: detect */
     int32_t token_budget;     /* length control (benches): <= 0 none */
     int32_t n_prefix;         /* previous-text prompt tokens before <|startoftranscript|> */
@@ -406,7 +416,7 @@ typedef struct osw_align_result {
 } osw_align_result;
 /* Teacher-forced decoder pass over the cross-K/V still resident from the last
  * osw_encode_windows / osw_decode_windows / osw_transcribe_batch call, for n distinct
- * windows of it: the alignment heads' softmax over the 1500 keys, cropped to F frames,
+ * windows of it: the alignment heads' softmax over the n_audio_ctx keys, cropped to F frames,
  * normalised per (head, frame) over the positions, median-filtered along the frames, averaged
  * over the heads, rows [no_timestamps, tokens...] kept (the matrix M), then DTW over -M
  * (transformers' _dynamic_time_warping tie rule) and the first frame of each token.  A
@@ -453,8 +463,8 @@ int osw_debug_gemm(osw_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t varian
  * for a capture in progress.  They replace no reference interface: the reference's attention
  * runs inside CTranslate2 [upstream].
  *
- * Encoder self-attention softmax(Q Kᵀ / 8) V over the T = 1500 positions: qkv fp16
- * [3][nb][H][1500][64] (the QKV GEMM's head-major output), out fp16 [nb * 1500][H * 64].  nb <= 64
+ * Encoder self-attention softmax(Q Kᵀ / 8) V over the context's T = n_audio_ctx positions: qkv fp16
+ * [3][nb][H][T][64] (the QKV GEMM's head-major output), out fp16 [nb * T][H * 64].  nb <= 64
  * and H <= 20 are independent of the context's dims.  form 0: the production launcher's choice
  * (64-query workgroups below 512 units of 128, lazy running max, unpipelined, unless the OSW_ATTN_*
  * environment says otherwise); an explicit form is OSW_ATTN_FORM | any of _EAGER (rescale O on
@@ -465,16 +475,20 @@ int osw_debug_gemm(osw_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t varian
 #define OSW_ATTN_FORM_PIPE 8
 int osw_debug_enc_attn(osw_ctx* ctx, const void* qkv, int32_t nb, int32_t H, int32_t form, void* out);
 /* Decoder cross-attention of `rows` = windows x beam decoder rows (beam <= 8, windows <= max_batch)
- * over each window's 1500 encoder keys, with the context's n_text_head heads H and width D = 64 H:
+ * over each window's T = n_audio_ctx encoder keys, with the context's n_text_head heads H and width D = 64 H:
  * q_slabs fp32 [ks][rows][D] are the q projection's split-K partials (q = fp16(bias + their sum)),
- * bias [D] or NULL, K and V fp16 [windows][H][1500][64]; out fp32 [rows][D] = the kernel's fp16
- * hi + lo output pair, summed.  legacy != 0 passes no workspace, which selects the one-workgroup-
+ * bias [D] or NULL, K and V fp16 [windows][H][T][64]; out fp32 [rows][D] = the kernel's fp16
+ * hi + lo output pair, summed.  legacy 1 passes no workspace, which selects the one-workgroup-
  * per-(row, head) kernel; otherwise the key-chunk kernels run: beam 1 and ks > 8 the VALU form,
- * beam > 1 with ks <= 8 the MFMA form.  The context's arrival tickets it used are zero on return. */
+ * beam > 1 with ks <= 8 the MFMA form, in the instantiation the decoder's launcher picks at T
+ * (legacy 0: ceil(ceil(T / 8) / 32) keys per lane, ceil(ceil(T / 8) / 64) key tiles per wave) or the
+ * full-width one that serves T > 1280 (legacy 2: 6 keys per lane, 3 tiles per wave).  The device
+ * copies of K and V are followed by 64 NaN keys, so a load past a window's T keys shows in `out`.
+ * The context's arrival tickets it used are zero on return. */
 int osw_debug_dec_xattn(osw_ctx* ctx, const float* q_slabs, int32_t ks, const float* bias, const void* K,
                         const void* V, int32_t rows, int32_t beam, int32_t legacy, float* out);
 /* The same launch with a window map (osw_decode_window_list's form): K and V fp16
- * [kv_windows][H][1500][64], kv_windows <= max_batch, and row group w (rows w * beam .. + beam - 1)
+ * [kv_windows][H][T][64], kv_windows <= max_batch, and row group w (rows w * beam .. + beam - 1)
  * attends window window_map[w]; window_map holds rows / beam distinct indices below kv_windows (else
  * OSW_EINVAL).  Equals osw_debug_dec_xattn over K[window_map], V[window_map] bit for bit. */
 int osw_debug_dec_xattn_windows(osw_ctx* ctx, const float* q_slabs, int32_t ks, const float* bias, const void* K,
@@ -591,7 +605,7 @@ int osw_debug_enc_layernorm(osw_ctx* ctx, int32_t M, int32_t M_alloc, int32_t D,
 int osw_debug_get_logmel(osw_ctx* ctx, int32_t clip, float* out, int64_t out_floats, float* clip_max);
 /* mel_window_kernel alone on n <= max_batch windows of the resident log-mel: the windows are checked
  * as osw_encode_windows checks them (OSW_EINVAL with the same message, before any launch), then
- * out_halfs receives the conv stem's operand X1 [n][3002][C1] as fp16 bits, C1 = n_mels rounded up
+ * out_halfs receives the conv stem's operand X1 [n][2 * n_audio_ctx + 2][C1] ([n][3002][C1] at the default) as fp16 bits, C1 = n_mels rounded up
  * to a multiple of 64: row 1 + t is frame seek + t, normalised; rows 0 and 3001, rows past the
  * segment and columns past n_mels are zero.  out_count: the buffer's size in fp16 elements. */
 int osw_debug_mel_windows(osw_ctx* ctx, const osw_window* windows, int32_t n, void* out_halfs, int64_t out_count);

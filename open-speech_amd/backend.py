@@ -32,6 +32,7 @@ import numpy as np
 
 from . import model_store
 from .audio import decode_audio_bytes
+from .dims import check_chunk_length
 from .runner import BatchRunner
 from .segments import TranscribeOptions, shape_response
 from .tokenizer import WhisperTokenizer
@@ -116,7 +117,11 @@ class HipWhisperBackend:
             if model_id in self._models:
                 logger.info("Model %s already loaded", model_id)
                 return
-            src = model_store.resolve(model_id, self._settings.get("stt_model_dir", None))
+            # STT_HIP_CHUNK_LENGTH: faster-whisper's chunk_length, whole seconds 1..30 (default 30),
+            # fixed when the model loads: its engines encode 50 * chunk_length positions per window
+            chunk_length = check_chunk_length(os.environ.get("STT_HIP_CHUNK_LENGTH", "30"))
+            src = model_store.resolve(model_id, self._settings.get("stt_model_dir", None),
+                                      chunk_length=None if chunk_length == 30 else chunk_length)
             max_batch = int(os.environ.get("STT_HIP_MAX_BATCH", "16"))
             wait_ms = float(os.environ.get("STT_HIP_BATCH_WAIT_MS", "5"))
             gap_ms = float(os.environ.get("STT_HIP_BATCH_GAP_MS", "1"))
@@ -156,7 +161,7 @@ class HipWhisperBackend:
             tok = WhisperTokenizer(src.dims.n_vocab, src.tokenizer_json)
             runner = BatchRunner(engines, tok, max_wait_ms=wait_ms, gap_ms=gap_ms, split=split,
                                  continuous=continuous, refill_min=int(os.environ.get("STT_HIP_REFILL_MIN", "1")),
-                                 spread_ms=float(spread) if spread else None)
+                                 spread_ms=float(spread) if spread else None, chunk_length=chunk_length)
             self._models[model_id] = _Model(src, runner, tok, engines)
             now = time.time()
             self._loaded_at[model_id] = now

@@ -15,7 +15,7 @@ constexpr int ALIGN_DTW_ROWS = 511;  // DTW rows per window (T = text tokens + 1
 // Rows are the windows of the last encode call (one decoder row per window); slot[row] is
 // the window's index in the align call (-1: not aligned), len[row] its forced length.
 struct AlignCapture {
-    float* scores = nullptr;        // [slot][head_idx][pstride][1500] raw scaled scores, fp32
+    float* scores = nullptr;        // [slot][head_idx][pstride][TK] raw scaled scores, fp32
     const int* slot = nullptr;      // [rows]
     const int* len = nullptr;       // [rows]
     const int* layer_heads = nullptr;  // {head, head_idx} pairs grouped by layer
@@ -37,9 +37,9 @@ void launch_align_tail(const float* logits, int rows, int V, int eot, int ctx, c
                        const int* len, const int* head, const int* forced, float* token_logprob, int* cur_tok,
                        SelState* st, hipStream_t s);
 void launch_align_bump(int* pos, hipStream_t s);
-// scores -> M [slot][T = len - slot_head - 1][1500-float rows, F used]; stats: 2 floats per (slot, head,
+// scores -> M [slot][T = len - slot_head - 1][TK-float rows, F used]; stats: 2 floats per (slot, head,
 // position), colstats: 2 floats per (slot, head, frame)
-void launch_align_post(const float* scores, int n_slots, int n_heads, int pstride, const int* slot_len,
+void launch_align_post(const float* scores, int n_slots, int n_heads, int pstride, int TK, const int* slot_len,
                        const int* slot_head, const int* slot_frames, const int* slot_width, float* stats, float* colstats, float* M,
                        hipStream_t s);
 // DTW over x (neg: over -x) of slot i: x + i * xstride, rows of ldx floats, T[i] x F[i] cells.

@@ -14,7 +14,6 @@ namespace osw {
 
 namespace {
 constexpr int HD = 64;
-constexpr int T_KEYS = 1500;
 #include "headreduce.h"
 
 // block-wide max / sum of 256 threads in a fixed order (wave DPP tree, then waves 0..3)
@@ -163,16 +162,18 @@ __global__ __launch_bounds__(256) void align_tail_kernel(const float* __restrict
 __global__ void align_bump_kernel(int* pos) { *pos += 1; }
 
 // grid slots x heads x pstride: max and sum of exp over the keys of one captured score row.
-// The softmax runs over all 1500 keys and the crop to F frames follows it (transformers /
+// The softmax runs over all TK keys of the context's window (50 per second of chunk_length)
+// and the crop to F frames follows it (transformers /
 // CTranslate2 order); cropping first (openai-whisper) is `nk = F` here.
 __global__ __launch_bounds__(256) void align_softmax_stats_kernel(const float* __restrict__ scores, int n_heads,
-                                                                  int pstride, const int* __restrict__ slot_len,
+                                                                  int pstride, int TK,
+                                                                  const int* __restrict__ slot_len,
                                                                   float* __restrict__ stats) {
     __shared__ float red[4];
     const int p = blockIdx.x % pstride, sh = blockIdx.x / pstride, sl = sh / n_heads;
     if (p >= slot_len[sl]) return;
-    const int nk = T_KEYS;
-    const float* row = scores + (int64_t)blockIdx.x * T_KEYS;
+    const int nk = TK;
+    const float* row = scores + (int64_t)blockIdx.x * TK;
     float m = -INFINITY;
     for (int i = threadIdx.x; i < nk; i += 256) m = fmaxf(m, row[i]);
     m = block_max(m, red);
@@ -186,15 +187,15 @@ __global__ __launch_bounds__(256) void align_softmax_stats_kernel(const float* _
 }
 
 __device__ __forceinline__ float align_prob(const float* __restrict__ scores, const float* __restrict__ stats,
-                                            int64_t row, int f) {
-    return expf(scores[row * T_KEYS + f] - stats[2 * row]) / stats[2 * row + 1];
+                                            int64_t row, int f, int TK) {
+    return expf(scores[row * TK + f] - stats[2 * row]) / stats[2 * row + 1];
 }
 
 // grid (frame blocks, heads, slots): mean and population standard deviation over all the
 // forced positions of one (head, frame), positions in order
 __global__ __launch_bounds__(256) void align_colstats_kernel(const float* __restrict__ scores,
                                                              const float* __restrict__ stats, int n_heads, int pstride,
-                                                             const int* __restrict__ slot_len,
+                                                             int TK, const int* __restrict__ slot_len,
                                                              const int* __restrict__ slot_frames,
                                                              float* __restrict__ colstats) {
     const int f = blockIdx.x * 256 + threadIdx.x, hi = blockIdx.y, sl = blockIdx.z;
@@ -202,14 +203,14 @@ __global__ __launch_bounds__(256) void align_colstats_kernel(const float* __rest
     if (P <= 0 || f >= slot_frames[sl]) return;
     const int64_t row0 = ((int64_t)sl * n_heads + hi) * pstride;
     float sum = 0.f;
-    for (int p = 0; p < P; ++p) sum += align_prob(scores, stats, row0 + p, f);
+    for (int p = 0; p < P; ++p) sum += align_prob(scores, stats, row0 + p, f, TK);
     const float mean = sum / (float)P;
     float var = 0.f;
     for (int p = 0; p < P; ++p) {
-        const float d = align_prob(scores, stats, row0 + p, f) - mean;
+        const float d = align_prob(scores, stats, row0 + p, f, TK) - mean;
         var = fmaf(d, d, var);
     }
-    const int64_t o = 2 * ((row0 / pstride) * T_KEYS + f);
+    const int64_t o = 2 * ((row0 / pstride) * TK + f);
     colstats[o] = mean;
     colstats[o + 1] = sqrtf(var / (float)P);
 }
@@ -217,7 +218,8 @@ __global__ __launch_bounds__(256) void align_colstats_kernel(const float* __rest
 // median of the W normalised weights around frame f (reflect padding), W odd
 template <int WC>
 __device__ __forceinline__ float align_median(const float* __restrict__ scores, const float* __restrict__ stats,
-                                              const float* __restrict__ cs, int64_t row, int f, int F, int W) {
+                                              const float* __restrict__ cs, int64_t row, int f, int F, int W,
+                                              int TK) {
     constexpr int CAP = WC ? WC : ALIGN_MAX_WIDTH;
     const int w = WC ? WC : W, pad = w / 2;
     float v[CAP];
@@ -230,7 +232,7 @@ __device__ __forceinline__ float align_median(const float* __restrict__ scores, 
         int g = f + k - pad;
         g = g < 0 ? -g : g;
         g = g >= F ? 2 * (F - 1) - g : g;
-        v[k] = (align_prob(scores, stats, row, g) - cs[2 * g]) / cs[2 * g + 1];
+        v[k] = (align_prob(scores, stats, row, g, TK) - cs[2 * g]) / cs[2 * g + 1];
     }
     // full compare-exchange network (every pair, fixed loops: the array stays in registers)
 #pragma unroll
@@ -253,7 +255,7 @@ __device__ __forceinline__ float align_median(const float* __restrict__ scores, 
 __global__ __launch_bounds__(256) void align_matrix_kernel(const float* __restrict__ scores,
                                                            const float* __restrict__ stats,
                                                            const float* __restrict__ colstats, int n_heads,
-                                                           int pstride, const int* __restrict__ slot_len,
+                                                           int pstride, int TK, const int* __restrict__ slot_len,
                                                            const int* __restrict__ slot_head,
                                                            const int* __restrict__ slot_frames,
                                                            const int* __restrict__ slot_width, float* __restrict__ M) {
@@ -264,14 +266,14 @@ __global__ __launch_bounds__(256) void align_matrix_kernel(const float* __restri
     float acc = 0.f;
     for (int hi = 0; hi < n_heads; ++hi) {
         const int64_t sh = (int64_t)sl * n_heads + hi, row = sh * pstride + t + hd;
-        const float* cs = colstats + 2 * sh * T_KEYS;
+        const float* cs = colstats + 2 * sh * TK;
         float v;
-        if (!filter) v = (align_prob(scores, stats, row, f) - cs[2 * f]) / cs[2 * f + 1];
-        else if (W == 7) v = align_median<7>(scores, stats, cs, row, f, F, W);
-        else v = align_median<0>(scores, stats, cs, row, f, F, W);
+        if (!filter) v = (align_prob(scores, stats, row, f, TK) - cs[2 * f]) / cs[2 * f + 1];
+        else if (W == 7) v = align_median<7>(scores, stats, cs, row, f, F, W, TK);
+        else v = align_median<0>(scores, stats, cs, row, f, F, W, TK);
         acc += v;
     }
-    M[((int64_t)sl * pstride + t) * T_KEYS + f] = acc / (float)n_heads;
+    M[((int64_t)sl * pstride + t) * TK + f] = acc / (float)n_heads;
 }
 
 // One workgroup per window.  cost[i][j] = x[i-1][j-1] + min(cost[i-1][j-1], cost[i-1][j],
@@ -378,15 +380,15 @@ void launch_align_tail(const float* logits, int rows, int V, int eot, int ctx, c
 
 void launch_align_bump(int* pos, hipStream_t s) { align_bump_kernel<<<1, 1, 0, s>>>(pos); }
 
-void launch_align_post(const float* scores, int n_slots, int n_heads, int pstride, const int* slot_len,
+void launch_align_post(const float* scores, int n_slots, int n_heads, int pstride, int TK, const int* slot_len,
                        const int* slot_head, const int* slot_frames, const int* slot_width, float* stats, float* colstats, float* M,
                        hipStream_t s) {
-    const int fb = (T_KEYS + 255) / 256;
-    align_softmax_stats_kernel<<<n_slots * n_heads * pstride, 256, 0, s>>>(scores, n_heads, pstride, slot_len, stats);
-    align_colstats_kernel<<<dim3(fb, n_heads, n_slots), 256, 0, s>>>(scores, stats, n_heads, pstride, slot_len,
+    const int fb = (TK + 255) / 256;
+    align_softmax_stats_kernel<<<n_slots * n_heads * pstride, 256, 0, s>>>(scores, n_heads, pstride, TK, slot_len, stats);
+    align_colstats_kernel<<<dim3(fb, n_heads, n_slots), 256, 0, s>>>(scores, stats, n_heads, pstride, TK, slot_len,
                                                                       slot_frames, colstats);
-    align_matrix_kernel<<<dim3(fb, pstride, n_slots), 256, 0, s>>>(scores, stats, colstats, n_heads, pstride, slot_len,
-                                                                    slot_head, slot_frames, slot_width, M);
+    align_matrix_kernel<<<dim3(fb, pstride, n_slots), 256, 0, s>>>(scores, stats, colstats, n_heads, pstride, TK,
+                                                                    slot_len, slot_head, slot_frames, slot_width, M);
 }
 
 void launch_align_dtw(const float* x, int64_t xstride, int ldx, int neg, int n_slots, const int* T, const int* F,

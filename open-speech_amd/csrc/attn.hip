@@ -1,4 +1,5 @@
-// Encoder self-attention (non-causal, T = 1500, head_dim 64) for gfx950.
+// Encoder self-attention (non-causal, T = the context's n_audio_ctx: 1500, or 50 per second of a
+// shorter chunk_length; head_dim 64) for gfx950.
 //
 // Flash-style: one workgroup = 4 waves = 128 queries of one (window, head); each
 // wave owns 32 queries (two 16-query MFMA tiles).  K/V tiles of 64 keys are staged

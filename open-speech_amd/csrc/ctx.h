@@ -32,7 +32,7 @@ namespace osw {
 void launch_mel(const int16_t*, const int64_t*, const int64_t*, const int*, int, int, const float2*, const float*,
                 const int*, const int*, const int*, const float*, int, float*, int*, hipStream_t);
 void launch_mel_window(const float*, const int64_t*, const int*, const int*, const int*, const int*, const int*, int,
-                       int, int, h16*, hipStream_t);
+                       int, int, int, h16*, hipStream_t);
 void launch_mel_normalize(const float*, int64_t, int, int, const int*, int, float*, hipStream_t);
 void launch_enc_attn(const h16*, h16*, int, int, int, hipStream_t);
 void launch_enc_attn_form(const h16*, h16*, int, int, int, bool eager, bool small, bool pipe, int grid_cap,
@@ -42,7 +42,8 @@ uint64_t hash_stream_key(uint64_t, int64_t);
 void launch_dec_self_attn(const float*, int, const float*, h16*, h16*, const int*, int, int, int, h16*, int64_t,
                           const int*, int, const SelState*, hipStream_t, int pos_row = 0);
 void launch_dec_cross_attn(const float*, int, const float*, const h16*, const h16*, int, int, int, int, h16*, int64_t,
-                           float*, int*, const SelState*, hipStream_t, const int* wmap = nullptr);
+                           float*, int*, const SelState*, hipStream_t, const int* wmap = nullptr,
+                           bool full = false);  // full: the 6-key / 3-tile chunk forms at any T (debug A/B)
 void launch_dec_resid_ln(const float*, int, int, int, const float*, float*, const float*, const float*, h16*, int64_t,
                          const h16*, const float*, const int*, const int*, int, int, hipStream_t, int pos_row = 0);
 void launch_dec_reduce_gelu(const float*, int, int, int, const float*, h16*, int64_t, hipStream_t);
@@ -221,6 +222,8 @@ struct osw_ctx {
     int B = 0;    // max windows per call
     int R = 0;    // decoder row capacity (windows x beam hypotheses)
     int C1 = 0;   // conv1 input channels padded to a multiple of 64
+    int T = 0;    // encoder positions per window: d.n_audio_ctx = 50 * chunk_length (1500 at the 30 s default)
+    int NF = 0;   // mel frames per window, 2 * T
     std::vector<void*> owned;
     std::map<std::string, Tensor> w;
     std::shared_ptr<void> arena;  // weight arena, shared with sibling contexts (osw_create_sibling)
@@ -326,8 +329,6 @@ struct osw_ctx {
 };
 
 namespace osw {
-const int T_ENC = 1500;
-const int N_FR = 3000;
 
 void trace_graph(const osw_ctx* c, const char* what);
 hipEvent_t get_ev(osw_ctx* c);

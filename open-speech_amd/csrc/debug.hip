@@ -148,7 +148,7 @@ int osw_encoder_layer_debug(osw_ctx* c, int32_t layer, const float* x, float* y,
         std::lock_guard<std::mutex> lk(c->mu);
         DeviceScope dev_scope_((c->device));
         REQUIRE(c->finalized, "weights not finalized");
-        REQUIRE(T == T_ENC, "T must be 1500");
+        REQUIRE(T == c->T, "T must be the context's n_audio_ctx");
         REQUIRE(layer >= 0 && layer < c->d.n_audio_layer, "layer out of range");
         const int64_t n = (int64_t)T * c->d.n_audio_state;
         HIPCHK(hipMemcpyAsync(c->X, x, n * 4, hipMemcpyHostToDevice, c->stream));
@@ -229,13 +229,13 @@ int osw_debug_enc_attn(osw_ctx* c, const void* qkv, int32_t nb, int32_t H, int32
         DeviceScope dev_scope_((c->device));
         GateLock gate_(capture_gate());
         TmpBufs tmp;
-        const size_t n = (size_t)nb * H * T_ENC * 64;
+        const size_t n = (size_t)nb * H * c->T * 64;
         h16* dq = dalloc<h16>(3 * n, tmp.v);
         h16* dout = dalloc<h16>(n, tmp.v);
         HIPCHK(hipMemcpyAsync(dq, qkv, 3 * n * 2, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemsetAsync(dout, 0xff, n * 2, c->stream));  // NaN: an unwritten element shows
-        if (form == 0) launch_enc_attn(dq, dout, T_ENC, H, nb, c->stream);
-        else launch_enc_attn_form(dq, dout, T_ENC, H, nb, (form & 2) != 0, !(form & 4), (form & 8) != 0, 1 << 30, c->stream);
+        if (form == 0) launch_enc_attn(dq, dout, c->T, H, nb, c->stream);
+        else launch_enc_attn_form(dq, dout, c->T, H, nb, (form & 2) != 0, !(form & 4), (form & 8) != 0, 1 << 30, c->stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(out, dout, n * 2, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -252,6 +252,9 @@ int debug_dec_xattn(osw_ctx* c, const float* q_slabs, int32_t ks, const float* b
         REQUIRE(c && q_slabs && K && V && out, "null argument");
         REQUIRE(ks >= 1 && ks <= 32, "ks out of range");
         REQUIRE(beam >= 1 && beam <= MAX_BEAM && rows >= beam && rows % beam == 0, "rows must be windows x beam, beam <= 8");
+        REQUIRE(legacy >= 0 && legacy <= 2, "legacy: 0 (chunk kernels), 1 (one workgroup per row and head), 2 (full chunk forms)");
+        const bool full = legacy == 2;
+        legacy = legacy == 1;
         const int H = c->d.n_text_head, D = c->d.n_text_state, W = rows / beam;
         REQUIRE(W <= c->B, "more windows than the context's max_batch (its arrival tickets)");
         if (window_map) {
@@ -269,11 +272,15 @@ int debug_dec_xattn(osw_ctx* c, const float* q_slabs, int32_t ks, const float* b
         DeviceScope dev_scope_((c->device));
         GateLock gate_(capture_gate());
         TmpBufs tmp;
-        const size_t nq = (size_t)ks * rows * D, nkv = (size_t)kv_windows * H * T_ENC * 64, no = (size_t)rows * D;
+        const size_t nq = (size_t)ks * rows * D, nkv = (size_t)kv_windows * H * c->T * 64, no = (size_t)rows * D;
         float* dq = dalloc<float>(nq, tmp.v);
         float* db = dalloc<float>(D, tmp.v);
-        h16* dk = dalloc<h16>(nkv, tmp.v);
-        h16* dv = dalloc<h16>(nkv, tmp.v);
+        // 64 NaN keys behind the last key of K and V: a load past a window's T keys shows
+        const size_t canary = 64 * 64;
+        h16* dk = dalloc<h16>(nkv + canary, tmp.v);
+        h16* dv = dalloc<h16>(nkv + canary, tmp.v);
+        HIPCHK(hipMemsetAsync(dk + nkv, 0xff, canary * 2, c->stream));
+        HIPCHK(hipMemsetAsync(dv + nkv, 0xff, canary * 2, c->stream));
         h16* dout = dalloc<h16>(2 * no, tmp.v);  // hi, then lo
         int* dmap = nullptr;
         if (window_map) {
@@ -290,8 +297,8 @@ int debug_dec_xattn(osw_ctx* c, const float* q_slabs, int32_t ks, const float* b
         HIPCHK(hipMemcpyAsync(dv, V, nkv * 2, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemsetAsync(dout, 0xff, 2 * no * 2, c->stream));
         HIPCHK(hipMemsetAsync(st, 0, (size_t)rows * sizeof(SelState), c->stream));
-        launch_dec_cross_attn(dq, ks, (legacy && !bias) ? nullptr : db, dk, dv, rows, H, T_ENC, beam, dout, (int64_t)no, ws,
-                              c->xticket, st, c->stream, dmap);
+        launch_dec_cross_attn(dq, ks, (legacy && !bias) ? nullptr : db, dk, dv, rows, H, c->T, beam, dout, (int64_t)no, ws,
+                              c->xticket, st, c->stream, dmap, full);
         hipError_t e = hipGetLastError();
         // the tickets are zero between launches (the last arriver resets its own); after a
         // failed launch they may not be, and the decode path shares them
@@ -791,12 +798,12 @@ int osw_debug_mel_windows(osw_ctx* c, const osw_window* windows, int32_t n, void
         DeviceScope dev_scope_((c->device));
         REQUIRE(!c->sess, "a decode session is open on this context (osw_session_end first)");
         REQUIRE(n >= 1 && n <= c->B, "window count out of range");
-        const int64_t need = (int64_t)n * 3002 * c->C1;
+        const int64_t need = (int64_t)n * (c->NF + 2) * c->C1;
         REQUIRE(out_count >= need, "output buffer too small");
         const std::vector<int> hw = pack_windows(c, windows, n);  // a refused window: no launch
         HIPCHK(hipMemcpyAsync(c->win, hw.data(), hw.size() * 4, hipMemcpyHostToDevice, c->stream));
         launch_mel_window(c->logmel, c->mel_off_d, c->nframes_d, c->clip_max, c->win, c->win + n, c->win + 2 * n, n,
-                          c->d.n_mels, c->C1, c->X1, c->stream);
+                          c->d.n_mels, c->C1, c->NF, c->X1, c->stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(out_halfs, c->X1, (size_t)need * 2, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));

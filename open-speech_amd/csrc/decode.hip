@@ -120,8 +120,8 @@ __global__ __launch_bounds__(256) void dec_cross_attn_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------
-// Cross-attention split over fixed key chunks (flash-decoding).  The T = 1500 keys
-// of a (window, head) are cut into XCH = 8 fixed chunks of <= 192 keys; one
+// Cross-attention split over fixed key chunks (flash-decoding).  The T keys (1500 at the
+// 30 s window) of a (window, head) are cut into XCH = 8 fixed chunks of <= 192 keys; one
 // workgroup per (window, head, chunk) serves all `beam` decoder rows of the window.
 // Every lane first issues its 6 K and 6 V row pieces (12 x 16 B; 48 KB per
 // workgroup, the whole chunk in one HBM round trip), then reduces the rows' q from
@@ -135,8 +135,19 @@ __global__ __launch_bounds__(256) void dec_cross_attn_kernel(const float* __rest
 // batches get 8x the workgroups of one-per-(row, head) (B = 1: 160 instead of 20),
 // and beam rows read each K/V chunk once instead of once per row.
 // Lane map: kg = tid >> 3 (32 key groups), c = tid & 7 (dims 8c..8c+7); the lane
-// holds keys u*32 + kg (u = 0..5) of the chunk for both scores and P·V.  K/V loads are
+// holds keys u*32 + kg (u = 0..XUT-1) of the chunk for both scores and P·V.  K/V loads are
 // nontemporal (1.97 GB per step at 64 windows cannot stay in the 256 MB MALL): 90 -> 84 us.
+// Shorter windows (n_audio_ctx = T = 50 * chunk_length, 50..1500): a chunk holds
+// per = ceil(T / 8) keys, and no chunk is empty because (XCH - 1) * ceil(T / XCH) < T for
+// every T = 50 s, s = 1..30 (the last chunk's first key 7 * per is 49, 91, ..., 1316 for T = 50,
+// 100, ..., 1500; osw_create refuses any T that breaks it).  A lane's loads past the chunk's
+// last key are clamped to it, so at T = 250 (per = 32) five of the six would be duplicates:
+// the greedy kernel is instantiated for XUT = ceil(per / 32) = 1..6 keys per lane and the MFMA
+// kernel for NT = ceil(per / 64) = 1..3 key tiles per wave, chosen by the launcher.  The
+// skipped keys contributed p = 0 and no maximum, so the greedy forms give the same bits; the
+// MFMA forms assign keys to waves differently and differ by fp32 summation order only.
+// T > 1280 takes XUT = 6 and NT = 3, the forms the 30 s window has always launched.  Measured
+// at 64 windows: every shorter form is at or below the full one's time.
 constexpr int XCH = XCHUNKS, XKEYS = 192, XU = XKEYS / 32;
 static_assert(XCH == 8, "the (window, head) -> XCD map assumes 8 chunks");
 
@@ -180,7 +191,7 @@ __device__ __forceinline__ h16x4 ds_read_tr(const h16* p) {  // ds_read_b64_tr_b
     return __builtin_bit_cast(h16x4, v);
 }
 
-template <int NB>
+template <int NB, int XUT = XU>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 5 ? 4 : NB > 1 ? 5 : 1))) void dec_xattn_chunk_kernel(const float* __restrict__ part, int ks,
                                                               const float* __restrict__ bias,
                                                               const h16* __restrict__ xk, const h16* __restrict__ xv,
@@ -226,9 +237,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 5 ? 4 
             qb[k] = part[min(wv + 4, ks - 1) * slab + off];
         }
     }
-    h16x8 kf[XU], vf[XU];
+    h16x8 kf[XUT], vf[XUT];
 #pragma unroll
-    for (int u = 0; u < XU; ++u) {
+    for (int u = 0; u < XUT; ++u) {
         const int key = k0 + min(u * 32 + kg, nk - 1);
         kf[u] = __builtin_nontemporal_load((const h16x8*)(xk + hoff + (int64_t)key * HD + 8 * c));
         vf[u] = __builtin_nontemporal_load((const h16x8*)(xv + hoff + (int64_t)key * HD + 8 * c));
@@ -260,7 +271,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 5 ? 4 
     }
     __syncthreads();
     // scores (8 lanes per key, combined by 3 xor-shuffles) and the chunk max per row
-    float sc[NB][XU], mx[NB];
+    float sc[NB][XUT], mx[NB];
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
         mx[k] = -INFINITY;
@@ -278,7 +289,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 5 ? 4 
 #pragma unroll
         for (int i = 0; i < 4; ++i) q2[i] = h16x2{(h16)q[2 * i], (h16)q[2 * i + 1]};
 #pragma unroll
-        for (int u = 0; u < XU; ++u) {
+        for (int u = 0; u < XUT; ++u) {
             float d = 0.f;
             if constexpr (NB > 1) {
 #pragma unroll
@@ -309,7 +320,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 5 ? 4 
         const float m = fmaxf(fmaxf(rm[0][k], rm[1][k]), fmaxf(rm[2][k], rm[3][k]));
         mx[k] = m;
 #pragma unroll
-        for (int u = 0; u < XU; ++u) {
+        for (int u = 0; u < XUT; ++u) {
             const float pu = u * 32 + kg < nk ? __expf(sc[k][u] - m) : 0.f;
             ls[k] += pu;
 #pragma unroll
@@ -394,7 +405,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 5 ? 4 
 //               ds_read_b64_tr_b16 (the encoder attention's transposed read); B = P in the
 //               score registers as an fp16 hi/lo pair, two MFMAs, so P keeps ~22 bits as in
 //               the fp32 VALU form
-// Wave w: keys 48w .. 48w+47 (3 tiles of 16) for the scores and for P·V over all 64 dims
+// Wave w: keys 16 NT w .. 16 NT (w + 1) - 1 (NT tiles of 16; 48w .. 48w+47 at NT = 3, the form
+// of T > 1024) for the scores and for P·V over all 64 dims
 // (one max for the workgroup, exchanged before the exponentials); the 4 waves' P·V sums
 // meet in LDS in fixed order.
 // KLDS: K arrives like V, 8 rows x 128 B per wave-instruction (whole cache lines), and is
@@ -402,7 +414,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 5 ? 4 
 // fragment straight from HBM (16 keys x 64 B per wave-instruction: every line is touched
 // by two instructions, the pattern that streamed the logits matrix at 3.95 instead of
 // 5.4 TB/s, tools/gemv_probe.hip).  Same K elements in the same fragments: same results.
-template <int NB, bool KLDS = true>
+template <int NB, bool KLDS = true, int NT = 3>
 __global__ __launch_bounds__(256) void dec_xattn_mfma_kernel(const float* __restrict__ part, int ks,
                                                              const float* __restrict__ bias,
                                                              const h16* __restrict__ xk, const h16* __restrict__ xv,
@@ -410,8 +422,8 @@ __global__ __launch_bounds__(256) void dec_xattn_mfma_kernel(const float* __rest
                                                              int* __restrict__ ticket, h16* __restrict__ out,
                                                              int64_t lo_off, const SelState* __restrict__ st,
                                                              const int* __restrict__ wmap) {
-    static_assert(NB <= 16 && XKEYS == 192, "16 MFMA columns; 4 waves x 3 key tiles");
-    __shared__ __attribute__((aligned(16))) h16 Vl[XKEYS * HD];
+    static_assert(NB <= 16 && NT >= 1 && 64 * NT <= XKEYS, "16 MFMA columns; 4 waves x NT key tiles");
+    __shared__ __attribute__((aligned(16))) h16 Vl[64 * NT * HD];
     __shared__ __attribute__((aligned(16))) h16 qsh[16][HD];
     __shared__ float red[4][NB][HD];
     __shared__ float rm[4][16], rl[4][16], bsh[4][HD];
@@ -448,29 +460,29 @@ __global__ __launch_bounds__(256) void dec_xattn_mfma_kernel(const float* __rest
         qa[k] = part[min(wv, ks - 1) * slab + off];
         qb[k] = part[min(wv + 4, ks - 1) * slab + off];
     }
-    // K fragments of this wave's 3 key tiles (A operand), nontemporal, clamped to the chunk
-    h16x8 kf[3][2], kr[6];
+    // K fragments of this wave's NT key tiles (A operand), nontemporal, clamped to the chunk
+    h16x8 kf[NT][2], kr[2 * NT];
     if constexpr (KLDS) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
+        for (int i = 0; i < 2 * NT; ++i) {
             const int r = (i * 4 + wv) * 8 + (lane >> 3);
             kr[i] = __builtin_nontemporal_load((const h16x8*)(xk + hoff + (int64_t)(k0 + min(r, nk - 1)) * HD + 8 * (lane & 7)));
         }
     } else {
 #pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            const int key = k0 + min(16 * (3 * wv + t) + li, nk - 1);
+        for (int t = 0; t < NT; ++t) {
+            const int key = k0 + min(16 * (NT * wv + t) + li, nk - 1);
 #pragma unroll
             for (int s = 0; s < 2; ++s)
                 kf[t][s] = __builtin_nontemporal_load((const h16x8*)(xk + hoff + (int64_t)key * HD + 32 * s + 8 * g));
         }
     }
-    // V chunk: 24 pieces of 8 rows x 128 B, 6 per wave, into registers now and into LDS
+    // V chunk: 8 NT pieces of 8 rows x 128 B, 2 NT per wave, into registers now and into LDS
     // (16-B chunk XOR-swizzled by row) once they land.  Plain loads, not global_load_lds:
     // with LDS-DMA in flight hipcc drains vmcnt(0) before any use of an earlier load.
-    h16x8 vr[6];
+    h16x8 vr[2 * NT];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
+    for (int i = 0; i < 2 * NT; ++i) {
         const int r = (i * 4 + wv) * 8 + (lane >> 3);
         vr[i] = __builtin_nontemporal_load((const h16x8*)(xv + hoff + (int64_t)(k0 + min(r, nk - 1)) * HD + 8 * (lane & 7)));
     }
@@ -482,7 +494,7 @@ __global__ __launch_bounds__(256) void dec_xattn_mfma_kernel(const float* __rest
         // the K chunk into the V image (V goes there after the scores: the max exchange's
         // barrier below orders every wave's fragment reads before the V stores)
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
+        for (int i = 0; i < 2 * NT; ++i) {
             const int r = (i * 4 + wv) * 8 + (lane >> 3);
             *(h16x8*)&Vl[r * HD + (((lane & 7) ^ ((r >> 1) & 7)) * 8)] = kr[i];
         }
@@ -504,23 +516,23 @@ __global__ __launch_bounds__(256) void dec_xattn_mfma_kernel(const float* __rest
     const h16x8 qf0 = *(const h16x8*)&qsh[li][8 * g], qf1 = *(const h16x8*)&qsh[li][32 + 8 * g];
     if constexpr (KLDS) {
 #pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            const int r = 16 * (3 * wv + t) + li;
+        for (int t = 0; t < NT; ++t) {
+            const int r = 16 * (NT * wv + t) + li;
 #pragma unroll
             for (int s = 0; s < 2; ++s) kf[t][s] = *(const h16x8*)&Vl[r * HD + (((4 * s + g) ^ ((r >> 1) & 7)) * 8)];
         }
     }
     // scores: lane holds key 16(3wv + t) + 4g + i of row li
-    f32x4 sc[3];
+    f32x4 sc[NT];
     float mx = -INFINITY;
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
+    for (int t = 0; t < NT; ++t) {
         f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
         a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[t][0], qf0, a, 0, 0, 0);
         a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[t][1], qf1, a, 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int key = 16 * (3 * wv + t) + 4 * g + i;
+            const int key = 16 * (NT * wv + t) + 4 * g + i;
             a[i] = key < nk ? a[i] * 0.125f : -INFINITY;
             mx = fmaxf(mx, a[i]);
         }
@@ -534,9 +546,9 @@ __global__ __launch_bounds__(256) void dec_xattn_mfma_kernel(const float* __rest
     // p = exp(s - m) as an fp16 hi/lo pair in the score registers, which are already the
     // B operand of v_mfma_f32_16x16x16_f16 (lane: keys 4g .. 4g+3 of a tile, row li)
     float ls = 0.f;
-    h16x4 ph[3], pl[3];
+    h16x4 ph[NT], pl[NT];
 #pragma unroll
-    for (int t = 0; t < 3; ++t)
+    for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float pv = __expf(sc[t][i] - m);
@@ -548,7 +560,7 @@ __global__ __launch_bounds__(256) void dec_xattn_mfma_kernel(const float* __rest
     ls += xor_lane<32>(ls);
     if (g == 0) rl[wv][li] = ls;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
+    for (int i = 0; i < 2 * NT; ++i) {
         const int r = (i * 4 + wv) * 8 + (lane >> 3);
         *(h16x8*)&Vl[r * HD + (((lane & 7) ^ ((r >> 1) & 7)) * 8)] = vr[i];
     }
@@ -561,8 +573,8 @@ __global__ __launch_bounds__(256) void dec_xattn_mfma_kernel(const float* __rest
     {
         const int q4 = li >> 2, p4 = li & 3;
 #pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            const int ra = 48 * wv + 16 * t + 4 * g + q4;
+        for (int t = 0; t < NT; ++t) {
+            const int ra = 16 * NT * wv + 16 * t + 4 * g + q4;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
                 const int col = 16 * dt + 4 * p4;
@@ -1511,7 +1523,7 @@ void launch_dec_self_attn(const float* part, int ks, const float* bias, h16* kc,
 
 void launch_dec_cross_attn(const float* part, int ks, const float* bias, const h16* xk, const h16* xv, int B, int H,
                            int T, int beam, h16* out, int64_t lo_off, float* ws, int* ticket, const SelState* st,
-                           hipStream_t s, const int* wmap) {
+                           hipStream_t s, const int* wmap, bool full) {
     static const bool legacy = std::getenv("OSW_XATTN_LEGACY") != nullptr;  // A/B switch: one workgroup per (row, head)
     if (legacy || !ws) {
         dec_cross_attn_kernel<<<H * B, 256, 0, s>>>(part, ks, bias, xk, xv, H, B, T, beam, out, lo_off, wmap);
@@ -1519,6 +1531,11 @@ void launch_dec_cross_attn(const float* part, int ks, const float* bias, const h
     }
     const int W = B / beam;
     const unsigned grid = (unsigned)(((W * H + 7) / 8) * 8 * XCH);
+    // keys per chunk; the full forms (6 keys per lane, 3 key tiles per wave) hold any per <= XKEYS
+    static const bool full_env = std::getenv("OSW_XATTN_FULL") != nullptr;  // A/B switch (tools/chunk_length_bench.py)
+    full = full || full_env;
+    const int per = (T + XCH - 1) / XCH;
+    const int xu = full ? XU : (per + 31) / 32, nt = full ? 3 : (per + 63) / 64;
     static const bool valu_beam = std::getenv("OSW_XATTN_VALU") != nullptr;  // A/B switch
     if (beam > 1 && !valu_beam && ks <= 8) {
         static const bool kdirect = std::getenv("OSW_XATTN_KDIRECT") != nullptr;  // A/B switch
@@ -1526,13 +1543,35 @@ void launch_dec_cross_attn(const float* part, int ks, const float* bias, const h
             if (beam <= 5) dec_xattn_mfma_kernel<5, false><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap);
             else dec_xattn_mfma_kernel<8, false><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap);
         } else {
-            if (beam <= 5) dec_xattn_mfma_kernel<5><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap);
-            else dec_xattn_mfma_kernel<8><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap);
+#define OSW_XMFMA(NB_, NT_) \
+    dec_xattn_mfma_kernel<NB_, true, NT_><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap)
+            if (beam <= 5) {
+                if (nt == 1) OSW_XMFMA(5, 1);
+                else if (nt == 2) OSW_XMFMA(5, 2);
+                else OSW_XMFMA(5, 3);
+            } else {
+                if (nt == 1) OSW_XMFMA(8, 1);
+                else if (nt == 2) OSW_XMFMA(8, 2);
+                else OSW_XMFMA(8, 3);
+            }
+#undef OSW_XMFMA
         }
         return;
     }
     switch (beam) {
-        case 1: dec_xattn_chunk_kernel<1><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap); break;
+#define OSW_XCHUNK1(XU_) \
+    dec_xattn_chunk_kernel<1, XU_><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap)
+        case 1:
+            switch (xu) {
+                case 1: OSW_XCHUNK1(1); break;
+                case 2: OSW_XCHUNK1(2); break;
+                case 3: OSW_XCHUNK1(3); break;
+                case 4: OSW_XCHUNK1(4); break;
+                case 5: OSW_XCHUNK1(5); break;
+                default: OSW_XCHUNK1(6); break;
+            }
+            break;
+#undef OSW_XCHUNK1
         case 2: dec_xattn_chunk_kernel<2><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap); break;
         case 3:
         case 4: dec_xattn_chunk_kernel<4><<<grid, 256, 0, s>>>(part, ks, bias, xk, xv, H, W, T, beam, ws, ticket, out, lo_off, st, wmap); break;

@@ -10,7 +10,7 @@ void align_capture(osw_ctx* c, int l, const float* part, int ks, int nb, int64_t
     const int first = a.layer_first[l], cnt = a.layer_first[l + 1] - first;
     if (cnt <= 0) return;
     launch_align_scores(part, ks, WF(c, "dec.l" + std::to_string(l) + ".xq.b"), c->XKV + (2 * l) * xkv_which, nb,
-                        c->d.n_text_head, T_ENC, a.layer_heads + 2 * first, cnt, a.n_heads, c->pos, a.slot, a.len,
+                        c->d.n_text_head, c->T, a.layer_heads + 2 * first, cnt, a.n_heads, c->pos, a.slot, a.len,
                         a.scores, a.pstride, c->stream);
 }
 
@@ -26,7 +26,7 @@ void align_capture(osw_ctx* c, int l, const float* part, int ks, int nb, int64_t
 void decoder_step_fused(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf) {
     const osw_dims& d = c->d;
     const int D = d.n_text_state, H = d.n_text_head, L = d.n_text_layer, ctx = d.n_text_ctx;
-    const int64_t xkv_which = (int64_t)(c->xkv_windows ? c->xkv_windows : nb / group) * H * T_ENC * 64;
+    const int64_t xkv_which = (int64_t)(c->xkv_windows ? c->xkv_windows : nb / group) * H * c->T * 64;
     const int64_t kv_layer = (int64_t)(c->kv_rows ? c->kv_rows : nb) * H * ctx * 64;
     const int64_t lo_d = (int64_t)c->R * D;
     float* xs[2] = {c->xd, c->xd2};
@@ -91,9 +91,9 @@ void decoder_step_fused(osw_ctx* c, int nb, int group, bool gather, const SelFus
         plain(c->dattn, p + ".o.w", D, D);
         fused(PRO_RESLN, resln(WF(c, p + ".o.b"), p + ".ln2", false), p + ".xq.w", D, D);
         {
-            Timed t(c, CL_XATTN, 2.0 * nb * H * (double)T_ENC * 64 * 2);
+            Timed t(c, CL_XATTN, 2.0 * nb * H * (double)c->T * 64 * 2);
             launch_dec_cross_attn(ps[last], ks, WF(c, p + ".xq.b"), c->XKV + (2 * l) * xkv_which,
-                                  c->XKV + (2 * l + 1) * xkv_which, nb, H, T_ENC, group, c->dattn, lo_d, c->xws,
+                                  c->XKV + (2 * l + 1) * xkv_which, nb, H, c->T, group, c->dattn, lo_d, c->xws,
                                   c->xticket, c->sel, c->stream, c->xmap);
         }
         if (c->acap) align_capture(c, l, ps[last], ks, nb, xkv_which);
@@ -124,7 +124,7 @@ void decoder_step_fused(osw_ctx* c, int nb, int group, bool gather, const SelFus
 bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf) {
     const osw_dims& d = c->d;
     const int D = d.n_text_state, H = d.n_text_head, L = d.n_text_layer, ctx = d.n_text_ctx;
-    const int64_t xkv_which = (int64_t)(c->xkv_windows ? c->xkv_windows : nb / group) * H * T_ENC * 64;
+    const int64_t xkv_which = (int64_t)(c->xkv_windows ? c->xkv_windows : nb / group) * H * c->T * 64;
     const int64_t kv_layer = (int64_t)(c->kv_rows ? c->kv_rows : nb) * H * ctx * 64;
     REQUIRE(nb <= c->R && D <= 1280, "decoder step: rows <= capacity and D <= 1280");
     REQUIRE(ctx <= 448, "decoder self-attention holds at most 448 positions");
@@ -189,9 +189,9 @@ bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf)
                             c->xdn, lo_d, nullptr, nullptr, nullptr, nullptr, ctx, d.n_vocab, c->stream);
         ks = partial(c->xdn, D, p + ".xq.w", D, D);
         {
-            Timed t(c, CL_XATTN, 2.0 * nb * H * (double)T_ENC * 64 * 2);
+            Timed t(c, CL_XATTN, 2.0 * nb * H * (double)c->T * 64 * 2);
             launch_dec_cross_attn(c->part, ks, WF(c, p + ".xq.b"), c->XKV + (2 * l) * xkv_which,
-                                  c->XKV + (2 * l + 1) * xkv_which, nb, H, T_ENC, group, c->dattn, lo_d, c->xws,
+                                  c->XKV + (2 * l + 1) * xkv_which, nb, H, c->T, group, c->dattn, lo_d, c->xws,
                                   c->xticket, c->sel, c->stream, c->xmap);
         }
         if (c->acap) align_capture(c, l, c->part, ks, nb, xkv_which);
@@ -644,7 +644,7 @@ void decode_refill(osw_ctx* c, int n_clips, const osw_decode_opts* o, osw_window
             pack.assign((size_t)k * (2 + P), 0);
             for (int i = 0; i < k; ++i) {
                 const int clip = next + i, row = free_rows[i];
-                wins[i] = osw_window{clip, 0, std::max(1, std::min(N_FR, c->nframes[clip] - 1))};
+                wins[i] = osw_window{clip, 0, std::max(1, std::min(c->NF, c->nframes[clip] - 1))};
                 slots[i] = row;
                 int* e = &pack[(size_t)i * (2 + P)];
                 e[0] = row;

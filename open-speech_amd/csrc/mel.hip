@@ -13,9 +13,9 @@
 // mel energies; log10 values are written TIME-major [clip][t][n_mels] (512 B
 // contiguous per frame) and the block max goes to one atomicMax per clip.
 //
-// Kernel 2 (mel_window_kernel): normalises ((max(v, gmax-8)+4)/4) a 3000-frame
+// Kernel 2 (mel_window_kernel): normalises ((max(v, gmax-8)+4)/4) an n_fr-frame
 // window [seek, seek+segment) into the fp16 conv1 operand X1[w][1+t][c] (zero
-// rows at t=-1 and t=3000, zero pad past the segment = faster-whisper pad_or_trim).
+// rows at t=-1 and t=n_fr, zero pad past the segment = faster-whisper pad_or_trim).
 #include "common.h"
 
 namespace osw {
@@ -169,23 +169,23 @@ __global__ void mel_max_init_kernel(int* clip_max, int n) {
     if (i < n) clip_max[i] = float_to_ordered(-INFINITY);
 }
 
-// X1[w][r][c], r in [0, 3002), c in [0, C1): fp16 normalised window, zero borders/pad
+// X1[w][r][c], r in [0, n_fr + 2), c in [0, C1): fp16 normalised window, zero borders/pad
 __global__ __launch_bounds__(256) void mel_window_kernel(
     const float* __restrict__ logmel, const int64_t* __restrict__ mel_off, const int* __restrict__ n_frames,
     const int* __restrict__ clip_max, const int* __restrict__ win_clip, const int* __restrict__ win_seek,
-    const int* __restrict__ win_size, int n_mels, int C1, h16* __restrict__ X1) {
+    const int* __restrict__ win_size, int n_mels, int C1, int n_fr, h16* __restrict__ X1) {
     const int w = blockIdx.y;
     const int clip = win_clip[w], seek = win_seek[w];
     const int seg = min(win_size[w], n_frames[clip] - seek);
     const float gmax = ordered_to_float(clip_max[clip]);
     const float floor_v = gmax - 8.0f;
-    const int64_t rows_total = 3002;
+    const int64_t rows_total = n_fr + 2;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < rows_total * C1;
          idx += (int64_t)gridDim.x * blockDim.x) {
         const int r = (int)(idx / C1), c = (int)(idx % C1);
         const int t = r - 1;
         float v = 0.f;
-        if (t >= 0 && t < 3000 && t < seg && c < n_mels) {
+        if (t >= 0 && t < n_fr && t < seg && c < n_mels) {
             const float x = logmel[mel_off[clip] + (int64_t)(seek + t) * n_mels + c];
             v = (fmaxf(x, floor_v) + 4.0f) * 0.25f;
         }
@@ -217,10 +217,10 @@ void launch_mel(const int16_t* pcm, const int64_t* offsets, const int64_t* mel_o
 
 void launch_mel_window(const float* logmel, const int64_t* mel_off, const int* n_frames, const int* clip_max,
                        const int* win_clip, const int* win_seek, const int* win_size, int n_windows, int n_mels,
-                       int C1, h16* X1, hipStream_t s) {
+                       int C1, int n_fr, h16* X1, hipStream_t s) {
     dim3 grid(256, n_windows);
     mel_window_kernel<<<grid, 256, 0, s>>>(logmel, mel_off, n_frames, clip_max, win_clip, win_seek, win_size,
-                                           n_mels, C1, X1);
+                                           n_mels, C1, n_fr, X1);
 }
 
 void launch_mel_normalize(const float* logmel, int64_t off, int nf, int n_mels, const int* clip_max, int clip,

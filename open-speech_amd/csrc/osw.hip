@@ -256,12 +256,12 @@ void setup_mel(osw_ctx* c) {
 void setup_workspace(osw_ctx* c) {
     const osw_dims& d = c->d;
     const int64_t B = c->B, De = d.n_audio_state, Dd = d.n_text_state;
-    const int64_t Me = B * T_ENC;
+    const int64_t Me = B * c->T;
     auto& o = c->owned;
     c->win = dalloc<int>(3 * B, o);
-    c->X1 = dalloc<h16>(B * 3002 * c->C1, o);
-    c->H1 = dalloc<h16>(B * 3001 * De, o);
-    HIPCHK(hipMemsetAsync(c->H1, 0, (size_t)B * 3001 * De * 2, c->stream));  // row 0 of every window stays zero
+    c->X1 = dalloc<h16>(B * (c->NF + 2) * c->C1, o);
+    c->H1 = dalloc<h16>(B * (c->NF + 1) * De, o);
+    HIPCHK(hipMemsetAsync(c->H1, 0, (size_t)B * (c->NF + 1) * De * 2, c->stream));  // row 0 of every window stays zero
     c->X = dalloc<float>(Me * De, o);
     c->Xn = dalloc<h16>(Me * De, o);
     c->QKV = dalloc<h16>(3 * Me * De, o);
@@ -376,15 +376,15 @@ void run_gemm(osw_ctx* c, const GemmArgs& g0, int cls) {
 void encoder_layer(osw_ctx* c, int i, int nb) {
     const osw_dims& d = c->d;
     const int De = d.n_audio_state, H = d.n_audio_head;
-    const int M = nb * T_ENC;
+    const int M = nb * c->T;
     const std::string p = "enc.l" + std::to_string(i);
     launch_layernorm(c->X, M, De, WF(c, p + ".ln1.g"), WF(c, p + ".ln1.b"), c->Xn, c->stream);
     GemmArgs g = gemm_plain(c->Xn, De, WH(c, p + ".qkv.w"), WF(c, p + ".qkv.b"), M, 3 * De, De, c->QKV, 0, EPI_HEADS);
-    g.heads_T = T_ENC; g.heads_H = H; g.heads_nb = nb;
+    g.heads_T = c->T; g.heads_H = H; g.heads_nb = nb;
     run_gemm(c, g, CL_ENC_GEMM);
     {
-        Timed t(c, CL_ENC_ATTN, 4.0 * nb * H * (double)T_ENC * T_ENC * 64);
-        launch_enc_attn(c->QKV, c->O, T_ENC, H, nb, c->stream);
+        Timed t(c, CL_ENC_ATTN, 4.0 * nb * H * (double)c->T * c->T * 64);
+        launch_enc_attn(c->QKV, c->O, c->T, H, nb, c->stream);
         HIPCHK(hipGetLastError());
     }
     run_gemm(c, gemm_plain(c->O, De, WH(c, p + ".o.w"), WF(c, p + ".o.b"), M, De, De, c->X, De, EPI_F32_RESID),
@@ -397,7 +397,7 @@ void encoder_layer(osw_ctx* c, int i, int nb) {
 }
 
 // The windows of one launch_mel_window, checked against the resident clips: clip, seek and size
-// (trimmed to a window's N_FR frames) as the kernel's three int arrays, [3][n].  encode() and
+// (trimmed to the window's NF = 2 T frames) as the kernel's three int arrays, [3][n].  encode() and
 // osw_debug_mel_windows both take their windows through here.
 std::vector<int> pack_windows(osw_ctx* c, const osw_window* wins, int n) {
     std::vector<int> hw(3 * (size_t)n);
@@ -407,7 +407,7 @@ std::vector<int> pack_windows(osw_ctx* c, const osw_window* wins, int n) {
         REQUIRE(wins[i].segment_size >= 1, "empty window");
         hw[i] = wins[i].clip;
         hw[n + i] = wins[i].seek;
-        hw[2 * n + i] = std::min(wins[i].segment_size, N_FR);
+        hw[2 * n + i] = std::min(wins[i].segment_size, c->NF);
     }
     return hw;
 }
@@ -458,30 +458,30 @@ void encode(osw_ctx* c, const osw_window* wins, int n, const int* slots) {
     {
         Timed t(c, CL_STAGE_ENC, 0);
         launch_mel_window(c->logmel, c->mel_off_d, c->nframes_d, c->clip_max, c->win, c->win + n, c->win + 2 * n, n,
-                          d.n_mels, c->C1, c->X1, c->stream);
+                          d.n_mels, c->C1, c->NF, c->X1, c->stream);
         // conv1: A row (w, t) = X1[w][t .. t+2][:] (3 rows of C1) ; C row -> H1[w][1 + t]
         GemmArgs g{};
-        g.A = c->X1; g.lda = c->C1; g.a_grp_rows = N_FR; g.a_grp_stride = 3002LL * c->C1;
+        g.A = c->X1; g.lda = c->C1; g.a_grp_rows = c->NF; g.a_grp_stride = (c->NF + 2LL) * c->C1;
         g.W = WH(c, "enc.conv1.w"); g.ldw = 3 * c->C1; g.bias = WF(c, "enc.conv1.b");
-        g.M = n * N_FR; g.N = De; g.K = 3 * c->C1;
-        g.C = c->H1 + De; g.ldc = De; g.c_grp_rows = N_FR; g.c_grp_stride = 3001LL * De; g.epi = EPI_F16_GELU;
+        g.M = n * c->NF; g.N = De; g.K = 3 * c->C1;
+        g.C = c->H1 + De; g.ldc = De; g.c_grp_rows = c->NF; g.c_grp_stride = (c->NF + 1LL) * De; g.epi = EPI_F16_GELU;
         run_gemm(c, g, CL_ENC_GEMM);
         // conv2 (stride 2): A row (w, t) = H1[w][2t .. 2t+2][:]  (H1 row r = input frame r-1)
         GemmArgs g2{};
-        g2.A = c->H1; g2.lda = 2LL * De; g2.a_grp_rows = T_ENC; g2.a_grp_stride = 3001LL * De;
+        g2.A = c->H1; g2.lda = 2LL * De; g2.a_grp_rows = c->T; g2.a_grp_stride = (c->NF + 1LL) * De;
         g2.W = WH(c, "enc.conv2.w"); g2.ldw = 3LL * De; g2.bias = WF(c, "enc.conv2.b");
-        g2.M = n * T_ENC; g2.N = De; g2.K = 3 * De;
-        g2.C = c->X; g2.ldc = De; g2.c_grp_rows = T_ENC; g2.c_grp_stride = (int64_t)T_ENC * De;
+        g2.M = n * c->T; g2.N = De; g2.K = 3 * De;
+        g2.C = c->X; g2.ldc = De; g2.c_grp_rows = c->T; g2.c_grp_stride = (int64_t)c->T * De;
         g2.pos = WF(c, "enc.pos"); g2.epi = EPI_F32_GELU_POS;
         run_gemm(c, g2, CL_ENC_GEMM);
         for (int i = 0; i < d.n_audio_layer; ++i) encoder_layer(c, i, n);
-        launch_layernorm(c->X, (int64_t)n * T_ENC, De, WF(c, "enc.lnpost.g"), WF(c, "enc.lnpost.b"), c->E, c->stream);
+        launch_layernorm(c->X, (int64_t)n * c->T, De, WF(c, "enc.lnpost.g"), WF(c, "enc.lnpost.b"), c->E, c->stream);
     }
     {
         Timed t(c, CL_STAGE_XKV, 0);
-        GemmArgs g = gemm_plain(c->E, De, WH(c, "dec.crosskv.w"), WF(c, "dec.crosskv.b"), n * T_ENC,
+        GemmArgs g = gemm_plain(c->E, De, WH(c, "dec.crosskv.w"), WF(c, "dec.crosskv.b"), n * c->T,
                                 d.n_text_layer * 2 * d.n_text_state, De, c->XKV, 0, EPI_HEADS);
-        g.heads_T = T_ENC; g.heads_H = d.n_text_head; g.heads_nb = n;
+        g.heads_T = c->T; g.heads_H = d.n_text_head; g.heads_nb = n;
         if (slots) {
             HIPCHK(hipMemcpyAsync(c->slot_d, slots, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
             g.heads_nb = c->B;
@@ -573,12 +573,12 @@ void align_reserve(osw_ctx* c, int n_slots, int pstride, int rows) {
     dfree(A.path, o);
     const int64_t S = A.cap_slots = std::max(A.cap_slots, n_slots), P = A.cap_pstride = std::max(A.cap_pstride, pstride),
                   NH = A.cap_heads = std::max(A.cap_heads, A.n_heads);
-    A.scores = dalloc<float>((size_t)(S * NH * P * T_ENC), o);
+    A.scores = dalloc<float>((size_t)(S * NH * P * c->T), o);
     A.stats = dalloc<float>((size_t)(S * NH * P * 2), o);
-    A.colstats = dalloc<float>((size_t)(S * NH * T_ENC * 2), o);
-    A.M = dalloc<float>((size_t)(S * P * T_ENC), o);
-    A.trace = dalloc<unsigned char>((size_t)(S * P * (T_ENC + 1)), o);
-    A.path = dalloc<int>((size_t)(S * 2 * (P + T_ENC)), o);
+    A.colstats = dalloc<float>((size_t)(S * NH * c->T * 2), o);
+    A.M = dalloc<float>((size_t)(S * P * c->T), o);
+    A.trace = dalloc<unsigned char>((size_t)(S * P * (c->T + 1)), o);
+    A.path = dalloc<int>((size_t)(S * 2 * (P + c->T)), o);
     ++A.gen;
 }
 
@@ -616,7 +616,7 @@ void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
         REQUIRE(W % 2 == 1 && W <= ALIGN_MAX_WIDTH, "align: median filter width must be odd and <= 15");
         len[a.window] = -1;  // seen
         if (a.n_tokens == 0) continue;  // no text: no work, empty results
-        const int F = std::min(T_ENC, a.num_frames / 2);
+        const int F = std::min(c->T, a.num_frames / 2);
         REQUIRE(F >= 1, "align: num_frames < 2");
         for (int t : {a.sot, en ? a.sot : a.language, en ? a.sot : a.task, a.no_timestamps})
             REQUIRE(t >= 0 && t < V, "align: bad special token");
@@ -702,10 +702,10 @@ void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
         HIPCHK(hipGetLastError());
     }
     c->acap = nullptr;
-    launch_align_post(A.scores, ns, A.n_heads, pstride, A.slot_len, A.slot_head, A.slot_frames, A.slot_width, A.stats,
+    launch_align_post(A.scores, ns, A.n_heads, pstride, c->T, A.slot_len, A.slot_head, A.slot_frames, A.slot_width, A.stats,
                       A.colstats, A.M, c->stream);
-    launch_align_dtw(A.M, (int64_t)pstride * T_ENC, T_ENC, 1, ns, A.slot_T, A.slot_frames, A.trace,
-                     (int64_t)pstride * (T_ENC + 1), A.path, pstride + T_ENC, A.path_len, A.tf, ctx, c->stream);
+    launch_align_dtw(A.M, (int64_t)pstride * c->T, c->T, 1, ns, A.slot_T, A.slot_frames, A.trace,
+                     (int64_t)pstride * (c->T + 1), A.path, pstride + c->T, A.path_len, A.tf, ctx, c->stream);
     HIPCHK(hipGetLastError());
     std::vector<int> tf((size_t)ns * ctx);
     std::vector<float> tp((size_t)ns * ctx);
@@ -957,7 +957,12 @@ int osw_create(const osw_dims* dims, int32_t device, int32_t max_batch, osw_ctx*
         REQUIRE(dims->n_audio_state % 128 == 0 && dims->n_text_state % 128 == 0, "model width must be a multiple of 128");
         REQUIRE(dims->n_audio_state / dims->n_audio_head == 64 && dims->n_text_state / dims->n_text_head == 64,
                 "head_dim must be 64");
-        REQUIRE(dims->n_audio_ctx == T_ENC, "n_audio_ctx must be 1500");
+        // the encoder window: chunk_length s = 1..30 seconds, 50 positions each.  Every such T keeps
+        // the last cross-attention key chunk non-empty (decode.hip, XCH); anything else is refused here
+        REQUIRE(dims->n_audio_ctx >= 50 && dims->n_audio_ctx <= 1500 && dims->n_audio_ctx % 50 == 0,
+                "n_audio_ctx must be 50 * chunk_length, chunk_length 1..30 (50, 100, ..., 1500)");
+        REQUIRE((XCHUNKS - 1) * ((dims->n_audio_ctx + XCHUNKS - 1) / XCHUNKS) < dims->n_audio_ctx,
+                "n_audio_ctx leaves a cross-attention key chunk empty");
         REQUIRE(dims->n_text_ctx <= 448, "n_text_ctx must be <= 448");
         REQUIRE(dims->n_audio_state == dims->n_text_state, "encoder and decoder width must match");
         REQUIRE(dims->n_audio_state <= 1280, "model width > 1280 unsupported");
@@ -973,6 +978,8 @@ int osw_create(const osw_dims* dims, int32_t device, int32_t max_batch, osw_ctx*
         c->B = max_batch;
         c->R = max_batch * 5;  // room for the reference's beam_size = 5 at full batch
         c->C1 = (dims->n_mels + 63) / 64 * 64;
+        c->T = dims->n_audio_ctx;
+        c->NF = 2 * c->T;
         if (const char* e = std::getenv("OSW_NO_GRAPH")) c->use_graph = !(e[0] == '1');
         // OSW_BATON_MIN_WINDOWS=n: encoders below n windows skip the baton (0: never skip)
         if (const char* e = std::getenv("OSW_BATON_MIN_WINDOWS")) c->baton_min = atoi(e);
@@ -1007,6 +1014,8 @@ int osw_create_sibling(osw_ctx* parent, int32_t max_batch, osw_ctx** out) {
         c->B = max_batch;
         c->R = max_batch * 5;
         c->C1 = parent->C1;
+        c->T = parent->T;
+        c->NF = parent->NF;
         c->use_graph = parent->use_graph;
         c->baton_min = parent->baton_min;
         DeviceScope dev_scope_((c->device));
@@ -1161,7 +1170,7 @@ int osw_get_encoder_output(osw_ctx* c, int32_t window, float* out, int64_t out_f
         std::lock_guard<std::mutex> lk(c->mu);
         DeviceScope dev_scope_((c->device));
         REQUIRE(window >= 0 && window < c->n_encoded, "window out of range");
-        const int64_t n = (int64_t)T_ENC * c->d.n_audio_state;
+        const int64_t n = (int64_t)c->T * c->d.n_audio_state;
         REQUIRE(out_floats >= n, "output buffer too small");
         std::vector<_Float16> tmp(n);
         HIPCHK(hipMemcpyAsync(tmp.data(), c->E + window * n, n * 2, hipMemcpyDeviceToHost, c->stream));
@@ -1267,7 +1276,7 @@ int osw_get_alignment_matrix(osw_ctx* c, int32_t window, float* out, int64_t out
         *F = A.F[sl];
         if (!out) return;
         REQUIRE(out_floats >= (int64_t)A.T[sl] * A.F[sl], "output buffer too small");
-        HIPCHK(hipMemcpy2DAsync(out, (size_t)A.F[sl] * 4, A.M + (int64_t)sl * A.pstride * T_ENC, (size_t)T_ENC * 4,
+        HIPCHK(hipMemcpy2DAsync(out, (size_t)A.F[sl] * 4, A.M + (int64_t)sl * A.pstride * c->T, (size_t)c->T * 4,
                                 (size_t)A.F[sl] * 4, A.T[sl], hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     });
@@ -1280,7 +1289,7 @@ int osw_transcribe_batch(osw_ctx* c, const int16_t* pcm, const int64_t* offsets,
         log_mel(c, pcm, offsets, n_clips, pcm_on_device, nullptr);
         std::vector<osw_window> wins(n_clips);
         for (int i = 0; i < n_clips; ++i)
-            wins[i] = osw_window{i, 0, std::max(1, std::min(N_FR, c->nframes[i] - 1))};
+            wins[i] = osw_window{i, 0, std::max(1, std::min(c->NF, c->nframes[i] - 1))};
         encode(c, wins.data(), n_clips);
         decode(c, n_clips, opts, res);
     });

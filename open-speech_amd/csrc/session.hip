@@ -69,7 +69,7 @@ int64_t store_alloc(osw_ctx* c, ClipStore& cs, int64_t len) {
         }
     // grow: a bigger arena holding the old one's contents at the same offsets
     const int64_t ncap = std::max<int64_t>(std::max<int64_t>(2 * cs.cap, cs.cap + len),
-                                           (int64_t)std::max(4, c->B) * 3001 * c->d.n_mels);
+                                           (int64_t)std::max(4, c->B) * (c->NF + 1) * c->d.n_mels);
     float* na = dalloc<float>((size_t)ncap, c->owned);
     if (cs.arena) {
         HIPCHK(hipMemcpyAsync(na, cs.arena, (size_t)cs.cap * 4, hipMemcpyDeviceToDevice, c->stream));
@@ -262,7 +262,7 @@ void session_admit(osw_ctx* c, int refill_min) {
     for (int i = 0; i < k; ++i) {
         const SessionWin& q = S->queue[i];
         const ClipStore::Clip& cl = cs.clips.at(q.clip);
-        const int len = std::max(1, std::min(std::min(q.w.segment_size, N_FR), cl.nframes - q.w.seek));
+        const int len = std::max(1, std::min(std::min(q.w.segment_size, c->NF), cl.nframes - q.w.seek));
         c->nframes[i] = len;
         c->mel_off[i + 1] = c->mel_off[i] + (int64_t)len * n_mels;
         src_off[i] = cl.off + (int64_t)q.w.seek * n_mels;

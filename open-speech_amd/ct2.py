@@ -31,6 +31,7 @@ import struct
 import numpy as np
 
 from .dims import WhisperDims
+from .weights import crop_positional
 
 _DT = {0: np.float32, 1: np.int8, 2: np.int16, 3: np.int32, 4: np.float16}
 _DT_ID = {np.dtype(np.float32): 0, np.dtype(np.int8): 1, np.dtype(np.int16): 2, np.dtype(np.int32): 3,
@@ -151,7 +152,7 @@ def ct2_to_canonical(v: dict, aliases: dict, d: WhisperDims) -> dict:
     w["enc.conv1.b"] = f32(g("encoder/conv1/bias"))
     w["enc.conv2.w"] = h16(g("encoder/conv2/weight").transpose(0, 2, 1))
     w["enc.conv2.b"] = f32(g("encoder/conv2/bias"))
-    w["enc.pos"] = f32(g("encoder/position_encodings/encodings"))
+    w["enc.pos"] = crop_positional(g("encoder/position_encodings/encodings"), d)
     for i in range(d.n_audio_layer):
         p, q = f"enc.l{i}", f"encoder/layer_{i}"
         w[p + ".ln1.g"] = f32(g(f"{q}/self_attention/layer_norm/gamma"))

@@ -7,7 +7,7 @@ the published Whisper architecture constants.
 """
 from __future__ import annotations
 
-from dataclasses import asdict, dataclass
+from dataclasses import asdict, dataclass, replace
 
 SAMPLE_RATE = 16000
 N_FFT = 400
@@ -17,6 +17,21 @@ N_SAMPLES = CHUNK_LENGTH * SAMPLE_RATE      # 480000 samples per 30 s window
 N_FRAMES = N_SAMPLES // HOP_LENGTH          # 3000 mel frames per window
 TIME_PRECISION = 0.02                       # seconds per timestamp token
 INPUT_STRIDE = 2                            # mel frames per encoder position
+FRAMES_PER_SECOND = SAMPLE_RATE // HOP_LENGTH   # 100 mel frames per second
+
+
+def check_chunk_length(s) -> int:
+    """faster-whisper's ``transcribe(chunk_length=...)``: whole seconds, 1 to 30 (the window a
+    loaded model encodes; 30 is Whisper's own).  Returns it as an int, refuses anything else."""
+    if isinstance(s, bool) or not isinstance(s, (int, float, str)) and not hasattr(s, "__index__"):
+        raise ValueError(f"chunk_length must be an integer number of seconds from 1 to 30, got {s!r}")
+    try:
+        f = float(s)
+    except (TypeError, ValueError):
+        raise ValueError(f"chunk_length must be an integer number of seconds from 1 to 30, got {s!r}") from None
+    if not (1 <= f <= CHUNK_LENGTH and f == int(f)):   # (NaN and the infinities fail the range test)
+        raise ValueError(f"chunk_length must be an integer number of seconds from 1 to 30, got {s!r}")
+    return int(f)
 
 
 @dataclass(frozen=True)
@@ -38,6 +53,22 @@ class WhisperDims:
 
     def as_dict(self) -> dict:
         return asdict(self)
+
+    @property
+    def chunk_length(self) -> int:
+        """Seconds of audio per encoder window: 50 encoder positions per second."""
+        return self.n_audio_ctx * INPUT_STRIDE // FRAMES_PER_SECOND
+
+    @property
+    def n_frames(self) -> int:
+        """Mel frames per encoder window (faster-whisper's nb_max_frames)."""
+        return self.n_audio_ctx * INPUT_STRIDE
+
+    def with_chunk_length(self, s) -> "WhisperDims":
+        """These dims with a window of ``s`` seconds: ``n_audio_ctx = 50 * s`` encoder positions,
+        which use the first ``50 * s`` rows of the positional table (crop_positional)."""
+        s = check_chunk_length(s)
+        return replace(self, n_audio_ctx=s * FRAMES_PER_SECOND // INPUT_STRIDE)
 
 
 # whisper-large-v3-turbo (808,878,080 params; SURVEY.md §2.2)

@@ -547,28 +547,32 @@ class WhisperEngine:
         return 1 | (2 if eager else 0) | (4 if qb128 else 0) | (8 if pipe else 0)
 
     def debug_enc_attn(self, qkv: np.ndarray, form: int = 0) -> np.ndarray:
-        """One encoder-attention launch: qkv fp16 [3][nb][H][1500][64] -> fp16 [nb*1500][H*64]."""
+        """One encoder-attention launch: qkv fp16 [3][nb][H][T][64] -> fp16 [nb*T][H*64], T the
+        engine's n_audio_ctx (1500 at the 30 s default window)."""
         qkv = np.ascontiguousarray(qkv, dtype=np.float16)
         three, nb, H, T, hd = qkv.shape
-        if (three, T, hd) != (3, 1500, 64):
-            raise ValueError("qkv must be [3][nb][H][1500][64]")
+        if (three, T, hd) != (3, self.dims.n_audio_ctx, 64):
+            raise ValueError(f"qkv must be [3][nb][H][{self.dims.n_audio_ctx}][64]")
         out = np.empty((nb * T, H * hd), np.float16)
         _lib.check(self.lib.osw_debug_enc_attn(self.ctx, qkv.ctypes.data_as(C.c_void_p), nb, H, int(form),
                                                out.ctypes.data_as(C.c_void_p)), "osw_debug_enc_attn")
         return out
 
     def debug_dec_xattn(self, q_slabs: np.ndarray, bias, K: np.ndarray, V: np.ndarray, beam: int = 1,
-                        legacy: bool = False) -> np.ndarray:
+                        legacy: bool | int = False) -> np.ndarray:
         """One decoder cross-attention launch: q_slabs fp32 [ks][rows][D], bias [D] or None, K and V
-        fp16 [W][H][1500][64], rows = W * beam -> fp32 [rows][D] (the hi + lo halves summed)."""
+        fp16 [W][H][T][64] (T the engine's n_audio_ctx), rows = W * beam -> fp32 [rows][D] (the hi + lo
+        halves summed).  ``legacy``: False / 0 the chunk kernels the decoder launches, True / 1 one
+        workgroup per (row, head), 2 the chunk kernels' full-width forms (6 keys per lane, 3 key tiles
+        per wave) whatever T is."""
         q = np.ascontiguousarray(q_slabs, dtype=np.float32)
         K = np.ascontiguousarray(K, dtype=np.float16)
         V = np.ascontiguousarray(V, dtype=np.float16)
         ks, rows, Dm = q.shape
         W, H = K.shape[:2]
-        if K.shape != (W, H, 1500, 64) or V.shape != K.shape or Dm != self.dims.n_text_state or \
+        if K.shape != (W, H, self.dims.n_audio_ctx, 64) or V.shape != K.shape or Dm != self.dims.n_text_state or \
                 H != self.dims.n_text_head or rows != W * beam:
-            raise ValueError("shapes: q [ks][W*beam][D], K/V [W][H][1500][64] with the engine's H and D")
+            raise ValueError("shapes: q [ks][W*beam][D], K/V [W][H][n_audio_ctx][64] with the engine's H and D")
         b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
         if b is not None and b.shape != (Dm,):
             raise ValueError("bias must be [D]")
@@ -577,14 +581,14 @@ class WhisperEngine:
         _lib.check(self.lib.osw_debug_dec_xattn(self.ctx, q.ctypes.data_as(fp), ks,
                                                 None if b is None else b.ctypes.data_as(fp),
                                                 K.ctypes.data_as(C.c_void_p), V.ctypes.data_as(C.c_void_p), rows,
-                                                int(beam), int(bool(legacy)), out.ctypes.data_as(fp)),
+                                                int(beam), int(legacy), out.ctypes.data_as(fp)),
                    "osw_debug_dec_xattn")
         return out
 
     def debug_dec_xattn_windows(self, q_slabs: np.ndarray, bias, K: np.ndarray, V: np.ndarray, window_map,
-                                beam: int = 1, legacy: bool = False) -> np.ndarray:
+                                beam: int = 1, legacy: bool | int = False) -> np.ndarray:
         """``debug_dec_xattn`` with a window map (osw_debug_dec_xattn_windows): K and V fp16
-        [kv_windows][H][1500][64], q_slabs fp32 [ks][len(window_map) * beam][D]; row group w
+        [kv_windows][H][T][64], q_slabs fp32 [ks][len(window_map) * beam][D]; row group w
         attends window ``window_map[w]``."""
         q = np.ascontiguousarray(q_slabs, dtype=np.float32)
         K = np.ascontiguousarray(K, dtype=np.float16)
@@ -592,9 +596,9 @@ class WhisperEngine:
         wm = np.ascontiguousarray([int(w) for w in window_map], dtype=np.int32).reshape(-1)
         ks, rows, Dm = q.shape
         KW, H = K.shape[:2]
-        if K.shape != (KW, H, 1500, 64) or V.shape != K.shape or Dm != self.dims.n_text_state or \
+        if K.shape != (KW, H, self.dims.n_audio_ctx, 64) or V.shape != K.shape or Dm != self.dims.n_text_state or \
                 H != self.dims.n_text_head or rows != len(wm) * beam:
-            raise ValueError("shapes: q [ks][len(window_map)*beam][D], K/V [kv_windows][H][1500][64] with the "
+            raise ValueError("shapes: q [ks][len(window_map)*beam][D], K/V [kv_windows][H][n_audio_ctx][64] with the "
                              "engine's H and D")
         b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
         if b is not None and b.shape != (Dm,):
@@ -605,7 +609,7 @@ class WhisperEngine:
         _lib.check(self.lib.osw_debug_dec_xattn_windows(self.ctx, q.ctypes.data_as(fp), ks,
                                                         None if b is None else b.ctypes.data_as(fp),
                                                         K.ctypes.data_as(C.c_void_p), V.ctypes.data_as(C.c_void_p),
-                                                        KW, mp, rows, int(beam), int(bool(legacy)),
+                                                        KW, mp, rows, int(beam), int(legacy),
                                                         out.ctypes.data_as(fp)), "osw_debug_dec_xattn_windows")
         return out
 
@@ -834,10 +838,11 @@ class WhisperEngine:
 
     def debug_mel_windows(self, windows: list) -> np.ndarray:
         """mel_window_kernel alone on (clip, seek, segment_size) windows of the resident log-mel
-        (osw_debug_mel_windows): the conv stem's operand X1 as fp16 [n][3002][C1]."""
+        (osw_debug_mel_windows): the conv stem's operand X1 as fp16 [n][2 * n_audio_ctx + 2][C1]
+        ([n][3002][C1] at the 30 s default window)."""
         arr = (_lib.osw_window * len(windows))(*[_lib.osw_window(int(c), int(s), int(z)) for c, s, z in windows])
         c1 = (self.dims.n_mels + 63) // 64 * 64
-        out = np.empty((len(windows), 3002, c1), np.float16)
+        out = np.empty((len(windows), 2 * self.dims.n_audio_ctx + 2, c1), np.float16)
         _lib.check(self.lib.osw_debug_mel_windows(self.ctx, arr, len(windows), out.ctypes.data_as(C.c_void_p),
                                                   out.size), "osw_debug_mel_windows")
         return out

@@ -62,7 +62,20 @@ def _snapshot_dirs(model_id: str, model_dir: str | None) -> list[str]:
     return cands
 
 
-def resolve(model_id: str, model_dir: str | None = None) -> ModelSource:
+def resolve(model_id: str, model_dir: str | None = None, chunk_length: int | None = None) -> ModelSource:
+    """``chunk_length`` (seconds, 1..30; None: the checkpoint's own window): the source's dims with
+    ``n_audio_ctx = 50 * chunk_length``; the loaders crop the encoder positional table to it."""
+    src = _resolve(model_id, model_dir)
+    if chunk_length is not None:
+        short = src.dims.with_chunk_length(chunk_length)
+        if short.n_audio_ctx > src.dims.n_audio_ctx:
+            raise ValueError(f"chunk_length {chunk_length} needs {short.n_audio_ctx} encoder positions; model "
+                             f"{model_id!r} has {src.dims.n_audio_ctx}")
+        src.dims = short
+    return src
+
+
+def _resolve(model_id: str, model_dir: str | None = None) -> ModelSource:
     if model_id.startswith("random:"):
         parts = model_id.split(":")
         preset = parts[1] if len(parts) > 1 else "large-v3-turbo"

@@ -34,6 +34,7 @@ still unanswered.
 """
 from __future__ import annotations
 
+import dataclasses
 import threading
 import time
 from collections import deque
@@ -42,6 +43,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from .dims import check_chunk_length
 from .segments import ClipResult, TranscribeOptions, session_supported, transcribe_clips
 from .tokenizer import WhisperTokenizer, get_suppressed_tokens
 
@@ -413,8 +415,12 @@ class _SessionLane(_Worker):
 class BatchRunner:
     def __init__(self, engines: list, tokenizer: WhisperTokenizer, max_wait_ms: float = 5.0,
                  gap_ms: float | None = None, split: bool = True, max_pace_ms: float = 100.0,
-                 continuous: bool = False, refill_min: int = 1, spread_ms: float | None = None):
+                 continuous: bool = False, refill_min: int = 1, spread_ms: float | None = None,
+                 chunk_length: int = 30):
         self.tokenizer = tokenizer
+        # seconds per encoder window of the engines' model (TranscribeOptions.chunk_length): a
+        # property of the loaded model, so every request's options carry the runner's value
+        self.chunk_length = check_chunk_length(chunk_length)
         self.max_wait_ms = max_wait_ms
         self.gap_ms = gap_ms
         self.split = split
@@ -497,6 +503,8 @@ class BatchRunner:
 
     def submit(self, pcm: np.ndarray, opts: TranscribeOptions) -> Future:
         f: Future = Future()
+        if opts.chunk_length != self.chunk_length:
+            opts = dataclasses.replace(opts, chunk_length=self.chunk_length)
         self.submit_req(_Req(np.ascontiguousarray(pcm, dtype=np.int16), opts, f))
         return f
 

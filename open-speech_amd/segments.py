@@ -12,7 +12,11 @@ for the parity mode — at temperature 0.0; the reference passes a scalar ``temp
 at ``src/backends/faster_whisper.py:238``, so there is no fallback, and a request with
 temperature > 0 takes faster-whisper's sampling branch: ``best_of`` samples per window,
 the best kept, and the previous-text prompt reset when temperature > 0.5):
-  content_frames = n_frames - 1; segment_size = min(3000, content_frames - seek)
+  content_frames = n_frames - 1; segment_size = min(nb_max_frames, content_frames - seek)
+  nb_max_frames = 100 * chunk_length (``TranscribeOptions.chunk_length``, seconds, 1..30, default 30:
+  faster-whisper's ``transcribe(chunk_length=...)``, restated from the upstream code, not pinned; the
+  window is zero-padded to nb_max_frames and the encoder runs on 50 * chunk_length positions, so the
+  engine's model must have been loaded with the same window: ``WhisperDims.with_chunk_length``)
   prompt = [<|startofprev|>] + previous_tokens[-223:] (if any) + [sot, lang, task]
   avg_logprob = sum_logprob / (len(tokens) + 1); compression_ratio of the window text
   skip window if no_speech_prob > 0.6 and avg_logprob < -1.0  (seek += segment_size)
@@ -56,7 +60,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .dims import HOP_LENGTH, INPUT_STRIDE, N_FRAMES, TIME_PRECISION
+from .dims import FRAMES_PER_SECOND, HOP_LENGTH, INPUT_STRIDE, TIME_PRECISION, check_chunk_length
 from .engine import DecodeConfig
 from .tokenizer import WhisperTokenizer, compression_ratio
 
@@ -105,8 +109,12 @@ class TranscribeOptions:
     # language detection only (faster-whisper WhisperModel.detect_language, one window): the
     # result carries the language and its probabilities, no segments
     detect_only: bool = False
+    # seconds of audio per encoder window (faster-whisper chunk_length; module docstring).  A
+    # property of the loaded model: the serving layer writes its own into every request
+    chunk_length: int = 30
 
     def __post_init__(self):
+        self.chunk_length = check_chunk_length(self.chunk_length)
         t = self.temperature
         if isinstance(t, (str, bytes)):
             raise ValueError(f"temperature must be a number or a sequence of numbers, got {t!r}")
@@ -134,7 +142,14 @@ class TranscribeOptions:
         # the fallback thresholds join only when they differ from the defaults, so the key of
         # every earlier configuration stays what it was
         th = (self.compression_ratio_threshold, self.log_prob_threshold, self.no_speech_threshold)
-        return self._key() + (() if th == (2.4, -1.0, 0.6) else (th,))
+        k = self._key() + (() if th == (2.4, -1.0, 0.6) else (th,))
+        # likewise the window length: the 30 s key is what it was, any other adds its field
+        return k if self.chunk_length == 30 else k + (("chunk_length", self.chunk_length),)
+
+    @property
+    def nb_max_frames(self) -> int:
+        """Mel frames per window: 100 * chunk_length."""
+        return FRAMES_PER_SECOND * self.chunk_length
 
     def _key(self):
         return (self.task, self.language, self.initial_prompt, self.condition_on_previous_text,
@@ -244,7 +259,7 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
         return [_english_clip(ClipResult(duration=len(p) / 16000.0), True) for p in pcm_list]
     nf = engine.log_mel(pcm_list)
     if opts.detect_only:
-        return _detect_clips(engine, pcm_list, nf, tok)
+        return _detect_clips(engine, pcm_list, nf, tok, opts.nb_max_frames)
     lang_token = _given_language(opts, tok)
     init_tokens = tok.encode(" " + opts.initial_prompt.strip()) if opts.initial_prompt else []
     states = []
@@ -281,7 +296,7 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
                 chunk = members[lo:lo + B]
                 wins = []
                 for s, _ in chunk:
-                    size = min(N_FRAMES, s.content_frames - s.seek)
+                    size = min(opts.nb_max_frames, s.content_frames - s.seek)
                     wins.append((s.idx, s.seek, size))
                 engine.encode(wins)
                 # (an English-only model's start sequence has no language token: nothing to name)
@@ -438,14 +453,14 @@ def _english_clip(res: ClipResult, want_probs: bool) -> ClipResult:
     return res
 
 
-def _detect_clips(engine, pcm_list: list, nf: list, tok: WhisperTokenizer) -> list[ClipResult]:
-    """TranscribeOptions.detect_only: the language of every clip's first 30 s window
+def _detect_clips(engine, pcm_list: list, nf: list, tok: WhisperTokenizer, nb_max_frames: int) -> list[ClipResult]:
+    """TranscribeOptions.detect_only: the language of every clip's first window (nb_max_frames frames)
     (faster-whisper ``detect_language`` with language_detection_segments = 1)."""
     out = []
     B = max(1, engine.max_batch)
     for lo in range(0, len(pcm_list), B):
         idx = list(range(lo, min(lo + B, len(pcm_list))))
-        engine.encode([(i, 0, max(1, min(N_FRAMES, nf[i] - 1))) for i in idx])
+        engine.encode([(i, 0, max(1, min(nb_max_frames, nf[i] - 1))) for i in idx])
         probs = engine.detect_language(len(idx))
         for i, p in zip(idx, probs):
             lang = tok.special.first_lang + int(np.argmax(p))
@@ -502,7 +517,7 @@ def next_window(s: _ClipState, opts: TranscribeOptions, tok: WhisperTokenizer) -
     """The clip's next window: seek, segment_size, prompt prefix, language, token budget."""
     prev = s.all_tokens[s.prompt_reset_since:]
     prefix = ([tok.special.sot_prev] + prev[-(448 // 2 - 1):]) if prev else []
-    size = min(N_FRAMES, s.content_frames - s.seek)
+    size = min(opts.nb_max_frames, s.content_frames - s.seek)
     budget = int(np.ceil(opts.tokens_per_second * size * FRAME_SEC)) + 2 if opts.tokens_per_second else 0
     lang = s.lang_token if tok.special.multilingual else None  # (English-only: no language token)
     return dict(seek=s.seek, segment_size=size, prefix=prefix, language_token=lang, token_budget=budget)

@@ -219,6 +219,17 @@ def sinusoids(length: int, channels: int, max_timescale: float = 10000.0) -> np.
     return np.concatenate([np.sin(t), np.cos(t)], axis=1).astype(np.float32)
 
 
+def crop_positional(table: np.ndarray, d: WhisperDims) -> np.ndarray:
+    """The first ``d.n_audio_ctx`` rows of a checkpoint's encoder positional table: a model
+    loaded with a shorter window (``WhisperDims.with_chunk_length``) encodes positions
+    0 .. 50 * chunk_length - 1 only, as faster-whisper's encoder does with a shorter input."""
+    table = np.asarray(table)
+    if table.ndim != 2 or table.shape[0] < d.n_audio_ctx:
+        raise ValueError(f"encoder positional table {table.shape} has fewer than n_audio_ctx = "
+                         f"{d.n_audio_ctx} rows")
+    return np.ascontiguousarray(table[:d.n_audio_ctx], dtype=np.float32)
+
+
 def make_tensor(spec: TensorSpec, d: WhisperDims, seed: int, stream: int) -> np.ndarray:
     shape = spec_shape(spec, d)
     if spec.kind == "sinusoid":
@@ -324,7 +335,7 @@ def from_hf_state_dict(sd: dict, d: WhisperDims) -> dict[str, np.ndarray]:
     w["enc.conv1.b"] = f32(g("model.encoder.conv1.bias"))
     w["enc.conv2.w"] = h16(g("model.encoder.conv2.weight").transpose(0, 2, 1))
     w["enc.conv2.b"] = f32(g("model.encoder.conv2.bias"))
-    w["enc.pos"] = f32(g("model.encoder.embed_positions.weight"))
+    w["enc.pos"] = crop_positional(g("model.encoder.embed_positions.weight"), d)
 
     def bias_or_zero(k, n):
         return g(k) if k in sd else np.zeros(n, np.float32)
