@@ -5,7 +5,7 @@
  * faster-whisper 1.2.1 / CTranslate2.  Each entry point names the reference
  * interface it replaces (paths under the reference repository):
  *
- *   osw_create / osw_set_weight / osw_init_weight_uniform / osw_finalize
+ *   osw_create / osw_set_weight / osw_set_weight_quant / osw_init_weight_uniform / osw_finalize
  *       replace   WhisperModel(model_id, device, compute_type, download_root)
  *                 called at src/backends/faster_whisper.py:40-45 (load_model :29-50)
  *   osw_destroy
@@ -38,7 +38,7 @@
  *       stage-level read-back and the DTW kernel alone, used only by the parity tests
  *   osw_debug_enc_attn / osw_debug_dec_xattn / osw_debug_dec_self_attn
  *       one attention launch on host data, used only by the parity tests
- *   osw_debug_dec_gemm / osw_debug_dec_resln / osw_debug_dec_gelu
+ *   osw_debug_dec_gemm / osw_debug_dec_gemm_quant / osw_debug_dec_resln / osw_debug_dec_gelu
  *       one launch of the decoder's hi/lo GEMMs, residual+LayerNorm and GELU reduce on host
  *       data, used only by the parity tests
  *   osw_debug_enc_gemm / osw_debug_enc_layernorm
@@ -252,6 +252,29 @@ int osw_set_weight(osw_ctx* ctx, const char* name, const void* host, int64_t nby
 /* Read one tensor back as stored on the device (enc.conv1.w: the padded [De][3][C1]
  * layout).  For tests and checkpoint round trips. */
 int osw_get_weight(osw_ctx* ctx, const char* name, void* host, int64_t nbytes);
+/* Int8 decoder weights (weight-only quantisation, STT_COMPUTE_TYPE=int8_float16): matrix `name`
+ * becomes W[n][k] ~ q[n][k] * mult[n], q int8 [N][K] row-major (n_q = N * K elements), mult fp32
+ * [N] (n_mult = N, every entry finite).  Accepted for the seven matrix kinds the skinny decoder
+ * GEMM streams: dec.tok and dec.lN.{qkv,o,xq,xo,fc1,fc2}.w; any other name, a wrong count or a K
+ * that is no multiple of 64 returns OSW_EINVAL.  The device then holds fp16(q) in the tensor
+ * itself (exact; what osw_get_weight returns for it), mult in "<name>.scale" and the int8
+ * fragment copy the skinny kernel streams in "<name>.frag".  The activations stay the hi/lo fp16
+ * pairs: the kernels run the float16 MFMA chain on fp16(q) and multiply each fp32 accumulator once
+ * by mult[n] before it leaves (a C or split-K slab element is fp32(acc * mult[n]); the bias is
+ * added after).  The state is per matrix and shared with sibling contexts, like the weights;
+ * osw_set_weight / osw_init_weight_uniform make the matrix float16 again.  Locking, capture gate
+ * and sibling rules are osw_set_weight's.  A change of kind (float16 <-> int8) is REFUSED
+ * (OSW_EINVAL) once this context holds decode graphs or sibling contexts exist: their graphs
+ * have the kernels of the old kind baked in (a destroyed sibling no longer counts).  An int8 dec.tok
+ * needs an int8 dec.l0.qkv.w (the embedding is that GEMM's prologue in the one-row step): the mix is
+ * refused by osw_finalize and by every decode call, at every batch size.  The opt-in OSW_GELU_TAIL / OSW_B1_ATTN_TAIL forms
+ * have no int8 kernels: a decode that would reach them with an int8 matrix returns an error. */
+/* (The three int8 entry points carry no digit in their names: the binding check matches [a-z_].) */
+int osw_set_weight_quant(osw_ctx* ctx, const char* name, const int8_t* q, const float* mult, int64_t n_q,
+                      int64_t n_mult);
+/* *out = 1 when matrix `name` holds int8 weights, else 0; a name that is not one of the seven
+ * matrix kinds above returns OSW_EINVAL. */
+int osw_weight_is_quant(osw_ctx* ctx, const char* name, int32_t* out);
 /* Device-side counter-hash init: x[i] = (2u-1)*scale + offset, u from splitmix64. */
 int osw_init_weight_uniform(osw_ctx* ctx, const char* name, uint64_t seed, int64_t stream,
                             float scale, float offset, int64_t zero_lo, int64_t zero_hi);
@@ -525,6 +548,29 @@ int osw_debug_dec_self_attn(osw_ctx* ctx, const float* qkv_slabs, int32_t ks, co
 int osw_debug_dec_gemm(osw_ctx* ctx, int32_t form, int32_t M, int32_t N, int32_t K, const void* A_hi,
                        const void* A_lo, const void* W, int32_t use_wf, float* out, int64_t out_floats,
                        int32_t* ks_out);
+/* osw_debug_dec_gemm's forms 0, 1 and 2 on int8 weights: W given as q int8 [N][K] plus mult fp32
+ * [N], A_hi and A_lo both required (int8 weights serve hi/lo rows), K a multiple of 64.  The
+ * device holds what osw_set_weight_quant leaves there.  use_q8_stream != 0: the skinny kernel
+ * streams the int8 fragments (GemmArgs::Wq); 0: the fp16(q) copy (row-major and fragment-major)
+ * with the multipliers, through the same launcher: the same bits.  The wide and tiled kernels
+ * read the row-major fp16(q) either way.  Forms 3 and 4 pass the same operands to the GELU-tail
+ * and attention-tail launchers, which refuse int8 weights before launching.  Same guard band,
+ * precondition checks and *ks_out as osw_debug_dec_gemm. */
+int osw_debug_dec_gemm_quant(osw_ctx* ctx, int32_t form, int32_t M, int32_t N, int32_t K, const void* A_hi,
+                          const void* A_lo, const int8_t* q, const float* mult, int32_t use_q8_stream,
+                          float* out, int64_t out_floats, int32_t* ks_out);
+/* Per-launch HIP-event time of launch_gemm_skinny_partial on one decoder projection shape (M <= 64
+ * hi/lo rows), float16 weights and int8 weights alternating in one call (tools/q8_bench.py): `warm`
+ * untimed launches of each, then `launches` timed ones, us_f16[i] / us_q8[i] microseconds.  Each
+ * stream exists in `copies` replicas walked round robin, so the weights come from where a decoder
+ * step finds them rather than from the L2 the previous launch filled. */
+int osw_debug_dec_gemm_time(osw_ctx* ctx, int32_t M, int32_t N, int32_t K, const void* A_hi, const void* A_lo,
+                            const int8_t* q, const float* mult, int32_t copies, int32_t warm, int32_t launches,
+                            float* us_f16, float* us_q8);
+/* While profiling (osw_set_profiling 2: eager decoder steps): the summed HIP-event time and the
+ * launch count of the fused (one-row) step's logits GEMM, which at batch 1 greedy carries the
+ * selection in its epilogue, since profiling was last set. */
+int osw_debug_logits_profile(osw_ctx* ctx, double* ms, int64_t* launches);
 /* Residual update + LayerNorm of `rows` rows of width D: x' = x + bias + Σ slabs (slabs fp32
  * [ks][rows][D], bias [D] or NULL), or with slabs == NULL the embedding entry x' = tok_emb[tok[r]]
  * + pos_emb[pos] (tok_emb fp16 [V][D], pos_emb fp32 [ctx][D], tok [rows], pos [rows] when pos_row

@@ -92,6 +92,9 @@ _SIGS = {
     "osw_create_sibling": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_void_p)]),
     "osw_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
     "osw_get_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    # int8 decoder weights (STT_COMPUTE_TYPE=int8_float16): q int8 [N][K], one fp32 multiplier per row
+    "osw_set_weight_quant": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, P(C.c_float), C.c_int64, C.c_int64]),
+    "osw_weight_is_quant": (C.c_int, [C.c_void_p, C.c_char_p, P(C.c_int32)]),
     "osw_init_weight_uniform": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int64, C.c_float, C.c_float,
                                           C.c_int64, C.c_int64]),
     "osw_finalize": (C.c_int, [C.c_void_p]),
@@ -147,6 +150,13 @@ _SIGS = {
     # one launch of the decoder's linear path on host data (parity tests)
     "osw_debug_dec_gemm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int32, P(C.c_float), C.c_int64, P(C.c_int32)]),
+    "osw_debug_dec_gemm_quant": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, P(C.c_float), C.c_int32, P(C.c_float), C.c_int64,
+                                        P(C.c_int32)]),
+    "osw_debug_dec_gemm_time": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, P(C.c_float), C.c_int32, C.c_int32, C.c_int32, P(C.c_float),
+                                          P(C.c_float)]),
+    "osw_debug_logits_profile": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_int64)]),
     "osw_debug_dec_resln": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), C.c_int32,
                                       P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), C.c_void_p,
                                       P(C.c_float), P(C.c_int32), P(C.c_int32), C.c_int32, C.c_int32, C.c_int32,

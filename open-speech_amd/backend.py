@@ -74,8 +74,9 @@ def _loaded_model_info(**kw):
 
 
 class _Model:
-    def __init__(self, src, runner, tokenizer, engines):
+    def __init__(self, src, runner, tokenizer, engines, compute_type="float16"):
         self.src, self.runner, self.tokenizer, self.engines = src, runner, tokenizer, engines
+        self.compute_type = compute_type   # the one in use, which loaded_models() reports
 
 
 class HipWhisperBackend:
@@ -128,7 +129,16 @@ class HipWhisperBackend:
             factory = self._engine_factory or _default_engine_factory
             engines = []
             try:
-                weights = model_store.load_weights(src)
+                # STT_COMPUTE_TYPE (the reference passes it to WhisperModel(compute_type=...)):
+                # int8_float16 / int8 select int8 decoder weights (stored int8 kept, float
+                # checkpoints quantised at load); anything else, or unset, is float16.  Random
+                # models have no weight files to quantise and stay float16.
+                asked = self._settings.get("stt_compute_type", None)
+                q8 = model_store.int8_decoder(asked)
+                weights = model_store.load_weights(src, asked) if q8 else model_store.load_weights(src)
+                compute_type = "int8_float16" if (q8 and weights is not None) else "float16"
+                if q8 and weights is None:
+                    logger.info("Model %s has no weight files: STT_COMPUTE_TYPE=%s ignored, float16", model_id, asked)
                 heads = model_store.alignment_heads(src)
                 for gpu in self._gpu_ids():
                     eng = factory(src.dims, gpu, max_batch)
@@ -162,11 +172,11 @@ class HipWhisperBackend:
             runner = BatchRunner(engines, tok, max_wait_ms=wait_ms, gap_ms=gap_ms, split=split,
                                  continuous=continuous, refill_min=int(os.environ.get("STT_HIP_REFILL_MIN", "1")),
                                  spread_ms=float(spread) if spread else None, chunk_length=chunk_length)
-            self._models[model_id] = _Model(src, runner, tok, engines)
+            self._models[model_id] = _Model(src, runner, tok, engines, compute_type)
             now = time.time()
             self._loaded_at[model_id] = now
             self._last_used[model_id] = now
-            logger.info("Model %s loaded on %s", model_id, self.device_label)
+            logger.info("Model %s loaded on %s (%s)", model_id, self.device_label, compute_type)
 
     def unload_model(self, model_id: str) -> None:
         m = self._models.pop(model_id, None)
@@ -184,7 +194,8 @@ class HipWhisperBackend:
         default_model = self._settings.get("stt_default_model", self._settings.get("stt_model", None))
         return [
             _loaded_model_info(
-                model=mid, backend=self.name, device=self.device_label, compute_type="float16",
+                model=mid, backend=self.name, device=self.device_label,
+                compute_type=getattr(self._models.get(mid), "compute_type", "float16"),
                 loaded_at=self._loaded_at[mid], last_used_at=self._last_used.get(mid),
                 is_default=(mid == default_model),
                 ttl_remaining=(None if (mid == default_model or ttl == 0)

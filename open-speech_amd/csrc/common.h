@@ -143,6 +143,17 @@ struct GemmArgs {
     // MFMA B fragment of one k32 step is 1 KB contiguous, so a wave's weight load is one
     // coalesced 1-KB piece instead of 16 rows x 64 B; launch_frag_pack), or nullptr
     const h16* Wf;
+    // int8 weights (weight-only: the activations stay hi/lo fp16 pairs), W[n][k] ~ q[n][k] * wscale[n].
+    // wscale: the fp32 multiplier of every output column; W then holds fp16(q) (exact) and each
+    // fp32 accumulator is multiplied once by wscale[n] before it leaves the kernel (a C element or
+    // a split-K slab element is fp32(acc * wscale[n]), one rounding; the bias is added after it).
+    // nullptr: float16 weights.  Served by the skinny and wide kernels with hi/lo rows.
+    const float* wscale;
+    // skinny kernel: the int8 fragment-major copy (launch_frag_pack_q8), streamed instead of Wf:
+    // [ceil(N/16)][K/64][64 lanes][16 B]; a lane's bytes 0-7 are its eight k values of k32 step
+    // 2j (k = 64 j + 8 (lane >> 4) + i, column 16 blk + (lane & 15)), bytes 8-15 those of step
+    // 2j + 1; each byte is q + 128 (unsigned).  Needs wscale.  nullptr: W / Wf are streamed.
+    const int8_t* Wq;
 };
 
 // fp32 -> (hi, lo) fp16 pair: hi = fp16(v), lo = fp16(v - hi)
@@ -156,6 +167,8 @@ __device__ __forceinline__ void split_h16(float v, h16* hi, h16* lo, int64_t i) 
 void launch_gemm(const GemmArgs& g, hipStream_t s);
 // W[N][ldw] (K columns used) -> its fragment-major copy Wf (GemmArgs::Wf), zero past N
 void launch_frag_pack(const h16* W, int64_t ldw, int N, int K, h16* Wf, hipStream_t s);
+// q int8 [N][K] row-major (K % 64 == 0) -> GemmArgs::Wq; columns past N hold q = 0 (byte 128)
+void launch_frag_pack_q8(const int8_t* q, int N, int K, int8_t* Wq, hipStream_t s);
 void launch_gemm_variant(const GemmArgs& g, int variant, hipStream_t s);  // 0 auto, 1 128-tile, 2 256-tile,
                                                                           // 4 8-phase 256, 5 wide, 6 64-tile ring, 7 64-tile;
                                                                           // debug: 8 8-phase fp16 out, 9 no epilogue, 10 GELU

@@ -45,7 +45,8 @@ void launch_dec_cross_attn(const float*, int, const float*, const h16*, const h1
                            float*, int*, const SelState*, hipStream_t, const int* wmap = nullptr,
                            bool full = false);  // full: the 6-key / 3-tile chunk forms at any T (debug A/B)
 void launch_dec_resid_ln(const float*, int, int, int, const float*, float*, const float*, const float*, h16*, int64_t,
-                         const h16*, const float*, const int*, const int*, int, int, hipStream_t, int pos_row = 0);
+                         const h16*, const float*, const int*, const int*, int, int, hipStream_t, int pos_row = 0,
+                         const float* tok_scale = nullptr);  // tok_scale: ResLnArgs::tok_scale (int8 embedding)
 void launch_dec_reduce_gelu(const float*, int, int, int, const float*, h16*, int64_t, hipStream_t);
 void launch_ingest_sumsq(const int16_t*, int, int, const int2*, int, float*, float*, hipStream_t);
 void launch_ingest_gain(const int16_t*, int64_t, int, int, float, int16_t*, hipStream_t);
@@ -106,6 +107,10 @@ struct Tensor {
     // a decoder matrix the skinny GEMM streams: N x K, with a fragment-major copy in the
     // tensor "<name>.frag" (GemmArgs::Wf), repacked whenever the matrix is written
     int frag_n = 0, frag_k = 0;
+    // such a matrix holds int8 weights (osw_set_weight_quant): this tensor is fp16(q), "<name>.scale"
+    // its row multipliers and "<name>.frag" the int8 fragments (GemmArgs::Wq).  Per matrix; the
+    // flag is shared with sibling contexts, as the arena is (null: not a matrix kind with a copy)
+    std::shared_ptr<std::atomic<int>> q8;
 };
 
 // The capture gate (one per process).  While a stream is being captured into a hipGraph,
@@ -227,6 +232,9 @@ struct osw_ctx {
     std::vector<void*> owned;
     std::map<std::string, Tensor> w;
     std::shared_ptr<void> arena;  // weight arena, shared with sibling contexts (osw_create_sibling)
+    // live sibling contexts on this arena (shared by all of them; osw_create_sibling / osw_destroy):
+    // their decode graphs cannot be seen from here, so a matrix keeps its kind while any exists
+    std::shared_ptr<std::atomic<int>> siblings;
     bool sibling = false;         // weights belong to another context: read-only here
     bool finalized = false;
     std::shared_ptr<EncBaton> baton;  // shared with sibling contexts; null: encoders not serialised
@@ -324,6 +332,10 @@ struct osw_ctx {
     // profiling
     bool prof = false;
     osw_profile pf{};
+    // the fused step's logits GEMM (batch-1: with the selection in its epilogue), per launch, while
+    // profiling (osw_debug_logits_profile; tools/q8_bench.py)
+    double logits_ms = 0;
+    int64_t logits_launches = 0;
     std::vector<EventPair> evs;
     std::vector<hipEvent_t> ev_free;
 };
@@ -334,7 +346,7 @@ void trace_graph(const osw_ctx* c, const char* what);
 hipEvent_t get_ev(osw_ctx* c);
 
 // class ids for per-launch accounting
-enum { CL_ENC_GEMM = 1, CL_ENC_ATTN = 2, CL_MEL = 3, CL_XATTN = 4, CL_STAGE_MEL = 10, CL_STAGE_ENC = 11,
+enum { CL_ENC_GEMM = 1, CL_ENC_ATTN = 2, CL_MEL = 3, CL_XATTN = 4, CL_LOGITS = 5, CL_STAGE_MEL = 10, CL_STAGE_ENC = 11,
        CL_STAGE_XKV = 12, CL_STAGE_DEC = 13 };
 
 struct Timed {
@@ -373,6 +385,11 @@ Tensor& W(osw_ctx* c, const std::string& n);
 const h16* WH(osw_ctx* c, const std::string& n);
 const float* WF(osw_ctx* c, const std::string& n);
 const h16* WFR(osw_ctx* c, const std::string& n);
+bool is_q8(osw_ctx* c, const std::string& n);  // the matrix holds int8 weights (osw_set_weight_quant)
+// the weight operands of a decoder GEMM on matrix n: W, Wf, and for int8 weights Wq and wscale
+void gemm_weights(osw_ctx* c, const std::string& n, GemmArgs& g);
+void require_embedding_kind(osw_ctx* c);  // an int8 dec.tok needs an int8 dec.l0.qkv.w (osw.hip)
+const float* tok_scale(osw_ctx* c);  // dec.tok's row multipliers when it is int8, else nullptr
 GemmArgs gemm_plain(const h16* A, int64_t lda, const h16* Wt, const float* bias, int M, int N, int K, void* C,
                     int64_t ldc, int epi);
 bool skinny_ok(const GemmArgs& g);

@@ -477,6 +477,186 @@ int osw_debug_dec_gemm(osw_ctx* c, int32_t form, int32_t M, int32_t N, int32_t K
     });
 }
 
+int osw_debug_dec_gemm_quant(osw_ctx* c, int32_t form, int32_t M, int32_t N, int32_t K, const void* A_hi, const void* A_lo,
+                          const int8_t* q, const float* mult, int32_t use_q8_stream, float* out, int64_t out_floats,
+                          int32_t* ks_out) {
+    return guard([&] {
+        REQUIRE(c && A_hi && A_lo && q && mult && out && ks_out, "null argument (int8 weights serve hi/lo rows)");
+        REQUIRE(form >= 0 && form <= 4, "form: 0 skinny slabs, 1 tiled slabs, 2 logits route, 3 GELU tail, 4 attention tail");
+        REQUIRE(M >= 1 && M <= 1024 && N >= 1 && N <= 65536 && K >= 64 && K <= 8192, "GEMM shape out of range");
+        REQUIRE(K % 64 == 0, "int8 fragments need K a multiple of 64");
+        for (int n = 0; n < N; ++n) REQUIRE(std::isfinite(mult[n]), "a multiplier is not finite");
+        int ks = 1;
+        bool skinny = true;
+        GemmArgs g = gemm_plain(nullptr, K, nullptr, nullptr, M, N, K, nullptr, N, EPI_F32);
+        if (form == 0 || form == 3 || form == 4) {
+            ks = skinny_ksplit(N, K);
+            require_skinny_split(K, ks);
+        } else if (form == 1) {
+            REQUIRE(N % 2 == 0, "the wide kernel needs an even N (8-byte stores)");
+            ks = tiled_ksplit(M, N, K);
+            REQUIRE(K % ks == 0 && (K / ks) % 64 == 0, "tiled split: K / ksplit a multiple of 64");
+            skinny = false;
+        } else {
+            skinny = skinny_ok(g);  // run_gemm's test (shape and epilogue only)
+            if (skinny) {
+                ks = skinny_ksplit(N, K);
+                require_skinny_split(K, ks);
+            } else {
+                REQUIRE(N % 2 == 0, "the wide kernel needs an even N (8-byte stores)");
+            }
+        }
+        const int64_t need = form == 2 ? (int64_t)M * N : (int64_t)ks * M * N;
+        REQUIRE(out_floats >= need && out_floats <= ((int64_t)1 << 27), "out_floats: the result's floats plus a guard band");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t na = (size_t)M * K, nw = (size_t)N * K;
+        h16* dA = dalloc<h16>(2 * na, tmp.v);
+        HIPCHK(hipMemcpyAsync(dA, A_hi, na * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dA + na, A_lo, na * 2, hipMemcpyHostToDevice, c->stream));
+        // what osw_set_weight_quant leaves on the device: fp16(q) row-major (and its fragment copy when
+        // that is the stream), the multipliers, the int8 fragments
+        std::vector<h16> half(nw);
+        for (size_t i = 0; i < nw; ++i) half[i] = (h16)(float)q[i];
+        DebugW dw;
+        upload_w(c, half.data(), N, K, !use_q8_stream, tmp, dw);
+        float* dm = dalloc<float>((size_t)N, tmp.v);
+        HIPCHK(hipMemcpyAsync(dm, mult, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+        g.A = dA;
+        g.A_lo = dA + na;
+        g.W = dw.w;
+        g.Wf = dw.wf;
+        g.wscale = dm;
+        if (use_q8_stream) {
+            int8_t* dq = dalloc<int8_t>(nw, tmp.v);
+            int8_t* dqf = dalloc<int8_t>((size_t)((N + 15) / 16) * 16 * K, tmp.v);
+            HIPCHK(hipMemcpyAsync(dq, q, nw, hipMemcpyHostToDevice, c->stream));
+            launch_frag_pack_q8(dq, N, K, dqf, c->stream);
+            HIPCHK(hipGetLastError());
+            g.Wq = dqf;
+        }
+        float* dout = result_buf(c, out_floats, tmp);
+        HIPCHK(hipStreamSynchronize(c->stream));  // before `half` goes, and before a refusal below
+        if (form == 0) {
+            const int got = launch_gemm_skinny_partial(g, dout, c->stream);
+            REQUIRE(got == ks, "launch_gemm_skinny_partial chose another split");
+        } else if (form == 1) {
+            launch_gemm_tiled_partial(g, dout, ks, c->stream);
+        } else if (form == 2) {
+            g.C = dout;
+            g.share_cus = c->share_cus;
+            if (skinny) {
+                float* part = dalloc<float>((size_t)ks * M * N, tmp.v);
+                launch_gemm_skinny(g, part, c->stream);
+            } else {
+                launch_gemm(g, c->stream);
+            }
+        } else if (form == 3) {  // the opt-in last-arriver tails: refused with int8 weights
+            ProArgs pt{};
+            launch_gemm_skinny_gelu_tail(g, dout, pt, c->stream);
+        } else {
+            ProArgs pa{};
+            launch_gemm_skinny_pro(g, PRO_RESLN, pa, false, dout, c->stream, false, true);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, dout, (size_t)out_floats * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        *ks_out = ks;
+    });
+}
+
+int osw_debug_dec_gemm_time(osw_ctx* c, int32_t M, int32_t N, int32_t K, const void* A_hi, const void* A_lo,
+                           const int8_t* q, const float* mult, int32_t copies, int32_t warm, int32_t launches,
+                           float* us_f16, float* us_q8) {
+    return guard([&] {
+        REQUIRE(c && A_hi && A_lo && q && mult && us_f16 && us_q8, "null argument");
+        REQUIRE(M >= 1 && M <= 64 && N >= 1 && N <= 65536 && K >= 128 && K <= 8192, "GEMM shape out of range");
+        REQUIRE(copies >= 1 && copies <= 1024 && warm >= 0 && launches >= 1 && launches <= 100000, "counts out of range");
+        const int ks = skinny_ksplit(N, K);
+        require_skinny_split(K, ks);
+        const size_t frag = (size_t)((N + 15) / 16) * 16 * K;   // elements of one fragment copy
+        REQUIRE(frag * 3 * (size_t)copies <= ((size_t)8 << 30), "more than 8 GiB of weight copies");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t na = (size_t)M * K, nw = (size_t)N * K;
+        h16* dA = dalloc<h16>(2 * na, tmp.v);
+        HIPCHK(hipMemcpyAsync(dA, A_hi, na * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dA + na, A_lo, na * 2, hipMemcpyHostToDevice, c->stream));
+        std::vector<h16> half(nw);
+        for (size_t i = 0; i < nw; ++i) half[i] = (h16)(float)q[i];
+        DebugW dw;
+        upload_w(c, half.data(), N, K, true, tmp, dw);
+        int8_t* dq = dalloc<int8_t>(nw, tmp.v);
+        HIPCHK(hipMemcpyAsync(dq, q, nw, hipMemcpyHostToDevice, c->stream));
+        float* dm = dalloc<float>((size_t)N, tmp.v);
+        HIPCHK(hipMemcpyAsync(dm, mult, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+        // `copies` replicas of each stream, walked round robin, so a launch finds its weights where a
+        // decoder step does (183 MB of other weights were read since their last use), not in the L2
+        h16* wf = dalloc<h16>(frag * copies, tmp.v);
+        int8_t* wq = dalloc<int8_t>(frag * copies, tmp.v);
+        launch_frag_pack_q8(dq, N, K, wq, c->stream);
+        HIPCHK(hipGetLastError());
+        for (int i = 0; i < copies; ++i) {
+            HIPCHK(hipMemcpyAsync(wf + frag * i, dw.wf, frag * 2, hipMemcpyDeviceToDevice, c->stream));
+            if (i) HIPCHK(hipMemcpyAsync(wq + frag * i, wq, frag, hipMemcpyDeviceToDevice, c->stream));
+        }
+        float* part = dalloc<float>((size_t)ks * M * N, tmp.v);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        GemmArgs g = gemm_plain(dA, K, dw.w, nullptr, M, N, K, nullptr, N, EPI_F32);
+        g.A_lo = dA + na;
+        hipEvent_t ev[4];
+        for (auto& e : ev) e = get_ev(c);
+        auto run = [&](int i, bool q8, hipEvent_t a, hipEvent_t b) {
+            GemmArgs h = g;
+            if (q8) {
+                h.Wq = wq + frag * (i % copies);
+                h.wscale = dm;
+            } else {
+                h.Wf = wf + frag * (i % copies);
+            }
+            if (a) HIPCHK(hipEventRecord(a, c->stream));
+            launch_gemm_skinny_partial(h, part, c->stream);
+            if (b) HIPCHK(hipEventRecord(b, c->stream));
+        };
+        try {
+            for (int i = 0; i < warm; ++i) {
+                run(i, false, nullptr, nullptr);
+                run(i, true, nullptr, nullptr);
+            }
+            for (int i = 0; i < launches; ++i) {   // float16 and int8 alternate, one event pair per launch
+                run(warm + i, false, ev[0], ev[1]);
+                run(warm + i, true, ev[2], ev[3]);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipStreamSynchronize(c->stream));
+                float a = 0.f, b = 0.f;
+                HIPCHK(hipEventElapsedTime(&a, ev[0], ev[1]));
+                HIPCHK(hipEventElapsedTime(&b, ev[2], ev[3]));
+                us_f16[i] = 1e3f * a;
+                us_q8[i] = 1e3f * b;
+            }
+        } catch (...) {
+            for (auto e : ev) c->ev_free.push_back(e);
+            throw;
+        }
+        for (auto e : ev) c->ev_free.push_back(e);
+    });
+}
+
+int osw_debug_logits_profile(osw_ctx* c, double* ms, int64_t* launches) {
+    return guard([&] {
+        REQUIRE(c && ms && launches, "null argument");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        resolve_events(c);
+        *ms = c->logits_ms;
+        *launches = c->logits_launches;
+    });
+}
+
 int osw_debug_dec_resln(osw_ctx* c, int32_t fused, int32_t direct, int32_t rows, int32_t D, const float* slabs,
                         int32_t ks, const float* bias, float* x, const float* gain, const float* shift,
                         const void* tok_emb, const float* pos_emb, const int32_t* tok, const int32_t* pos, int32_t ctx,

@@ -627,7 +627,7 @@ __global__ __launch_bounds__(256) void dec_xattn_mfma_kernel(const float* __rest
 __global__ __launch_bounds__(256) void dec_resid_ln_kernel(ResLnArgs A, h16* __restrict__ y, int64_t lo_off) {
     __shared__ __attribute__((aligned(16))) float red[resln_scratch(1, 1280)];
     const int b = blockIdx.x;
-    resln_rows<1, 8, true>(A, b, 1, true, red,
+    resln_rows<1, 8, true, EMB_ANY>(A, b, 1, true, red,
                   [&](int, int c, float v) { split_h16(v, y, y + lo_off, (int64_t)b * A.D + c); });
 }
 
@@ -1582,8 +1582,10 @@ void launch_dec_cross_attn(const float* part, int ks, const float* bias, const h
 
 void launch_dec_resid_ln(const float* part, int ks, int B, int D, const float* bias, float* x, const float* g,
                          const float* be, h16* y, int64_t lo_off, const h16* tok_emb, const float* pos_emb,
-                         const int* tok, const int* pos, int ctx, int V, hipStream_t s, int pos_row) {
-    ResLnArgs A{part, ks, (int64_t)B * D, bias, x, x, g, be, tok_emb, pos_emb, tok, pos, ctx, D, V, pos_row};
+                         const int* tok, const int* pos, int ctx, int V, hipStream_t s, int pos_row,
+                         const float* tok_scale) {
+    ResLnArgs A{part, ks, (int64_t)B * D, bias, x, x, g, be, tok_emb, pos_emb, tok, pos, ctx, D, V, pos_row,
+                tok_scale};
     dec_resid_ln_kernel<<<B, 256, 0, s>>>(A, y, lo_off);
 }
 

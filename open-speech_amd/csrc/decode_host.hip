@@ -34,7 +34,7 @@ void decoder_step_fused(osw_ctx* c, int nb, int group, bool gather, const SelFus
     int xi = 0, last = 1, ks = 0;  // residual buffer holding x; slab buffer of the last GEMM
     auto gemm = [&](const h16* A, const std::string& w, int N, int K) {
         GemmArgs g = gemm_plain(A, D, WH(c, w), nullptr, nb, N, K, nullptr, 0, EPI_F32);
-        g.Wf = WFR(c, w);
+        gemm_weights(c, w, g);
         g.A_lo = A ? A + lo_d : nullptr;
         return g;
     };
@@ -44,7 +44,7 @@ void decoder_step_fused(osw_ctx* c, int nb, int group, bool gather, const SelFus
         ProArgs pa{};
         pa.ln = ResLnArgs{embed ? nullptr : ps[last], ks, (int64_t)nb * D, bias, xs[xi], xs[xi ^ 1],
                           WF(c, ln + ".g"), WF(c, ln + ".b"), WH(c, "dec.tok"), WF(c, "dec.pos"), c->cur_tok, c->pos,
-                          ctx, D, d.n_vocab, c->row_pos ? 1 : 0};
+                          ctx, D, d.n_vocab, c->row_pos ? 1 : 0, embed ? tok_scale(c) : nullptr};
         xi ^= 1;
         return pa;
     };
@@ -67,6 +67,7 @@ void decoder_step_fused(osw_ctx* c, int nb, int group, bool gather, const SelFus
         return e && e[0] == '1';
     }();
     const bool attn_tail = attn_tail_on && nb == 1 && !gather && !c->acap;
+    // (opt-in, and refused with int8 weights by the launcher: never a silent float16 fall-back)
     for (int l = 0; l < L; ++l) {
         const std::string p = "dec.l" + std::to_string(l), pp = "dec.l" + std::to_string(l - 1);
         ProArgs pq = l == 0 ? resln(nullptr, p + ".ln1", true) : resln(WF(c, pp + ".fc2.b"), p + ".ln1", false);
@@ -109,7 +110,10 @@ void decoder_step_fused(osw_ctx* c, int nb, int group, bool gather, const SelFus
     gl.ldc = d.n_vocab;
     ProArgs pl_args = resln(WF(c, pl + ".fc2.b"), "dec.lnpost", false);
     if (sf) pl_args.sel = *sf;
-    launch_gemm_skinny_pro(gl, PRO_RESLN, pl_args, true, nullptr, c->stream, sf != nullptr);
+    {
+        Timed t(c, CL_LOGITS, 0);  // (profiling only)
+        launch_gemm_skinny_pro(gl, PRO_RESLN, pl_args, true, nullptr, c->stream, sf != nullptr);
+    }
     HIPCHK(hipGetLastError());
 }
 
@@ -127,6 +131,7 @@ bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf)
     const int64_t xkv_which = (int64_t)(c->xkv_windows ? c->xkv_windows : nb / group) * H * c->T * 64;
     const int64_t kv_layer = (int64_t)(c->kv_rows ? c->kv_rows : nb) * H * ctx * 64;
     REQUIRE(nb <= c->R && D <= 1280, "decoder step: rows <= capacity and D <= 1280");
+    require_embedding_kind(c);
     REQUIRE(ctx <= 448, "decoder self-attention holds at most 448 positions");
     // the decoder's GEMM operands are hi/lo fp16 pairs (fp32-accurate activations: the
     // logits stay within 1e-3 of an fp32 decoder); lo = hi + R rows
@@ -148,12 +153,13 @@ bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf)
             const int ks = tiled_ksplit(nb, N, K);
             REQUIRE((int64_t)ks * nb * N <= c->part_floats, "decoder workspace too small");
             GemmArgs g = gemm_plain(A, lda, Wt, nullptr, nb, N, K, nullptr, 0, EPI_F32);
+            gemm_weights(c, w, g);  // (the tiles read W; int8: with the multipliers in the epilogue)
             g.A_lo = A + lo;
             launch_gemm_tiled_partial(g, c->part, ks, c->stream);
             return ks;
         }
         GemmArgs g = gemm_plain(A, lda, Wt, nullptr, nb, N, K, nullptr, 0, EPI_F32);
-        g.Wf = WFR(c, w);
+        gemm_weights(c, w, g);
         g.A_lo = A + lo;
         REQUIRE((int64_t)skinny_ksplit(N, K) * nb * N <= c->part_floats, "split-K workspace too small");
         return launch_gemm_skinny_partial(g, c->part, c->stream);
@@ -173,7 +179,8 @@ bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf)
     const bool gelu_tail = !gelu_pro && nb <= 64 && gelu_tail_on && (4 * D) % 64 == 0;
     // x = tok_emb[tok] + pos_emb[pos]; xdn = LN1_0(x)
     launch_dec_resid_ln(nullptr, 0, nb, D, nullptr, c->xd, WF(c, "dec.l0.ln1.g"), WF(c, "dec.l0.ln1.b"), c->xdn, lo_d,
-                        WH(c, "dec.tok"), WF(c, "dec.pos"), c->cur_tok, c->pos, ctx, d.n_vocab, c->stream, c->row_pos);
+                        WH(c, "dec.tok"), WF(c, "dec.pos"), c->cur_tok, c->pos, ctx, d.n_vocab, c->stream, c->row_pos,
+                        tok_scale(c));
     for (int l = 0; l < L; ++l) {
         const std::string p = "dec.l" + std::to_string(l);
         int ks = partial(c->xdn, D, p + ".qkv.w", 3 * D, D);
@@ -205,7 +212,7 @@ bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf)
             // 9..64 rows: split-K fc1 whose last workgroup per column block reduces that
             // block's slabs + bias + GELU (TAIL_GELU): no reduce kernel
             GemmArgs g = gemm_plain(c->xdn, D, WH(c, p + ".fc1.w"), nullptr, nb, 4 * D, D, nullptr, 0, EPI_F32);
-            g.Wf = WFR(c, p + ".fc1.w");
+            gemm_weights(c, p + ".fc1.w", g);  // (int8: the launcher refuses the tail)
             g.A_lo = c->xdn + lo_d;
             ProArgs pt{};
             pt.bias = WF(c, p + ".fc1.b");
@@ -223,7 +230,7 @@ bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf)
             ProArgs pg{};
             pg.part = c->part; pg.ks = ks; pg.bias = WF(c, p + ".fc1.b");
             GemmArgs g = gemm_plain(nullptr, D, WH(c, p + ".fc2.w"), nullptr, nb, D, 4 * D, nullptr, 0, EPI_F32);
-            g.Wf = WFR(c, p + ".fc2.w");
+            gemm_weights(c, p + ".fc2.w", g);
             ks = launch_gemm_skinny_pro(g, PRO_GELU, pg, false, c->part2, c->stream);
             fc2_part = c->part2;
         } else {
@@ -236,7 +243,7 @@ bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf)
                             lo_d, nullptr, nullptr, nullptr, nullptr, ctx, d.n_vocab, c->stream);
     }
     GemmArgs gl = gemm_plain(c->xdn, D, WH(c, "dec.tok"), nullptr, nb, d.n_vocab, D, c->logits, d.n_vocab, EPI_F32);
-    gl.Wf = WFR(c, "dec.tok");  // used by the skinny kernel (< 24 rows); the wide kernel reads W
+    gemm_weights(c, "dec.tok", gl);  // Wf / Wq: the skinny kernel (< 24 rows); the wide kernel reads W
     gl.A_lo = c->xdn + lo_d;
     run_gemm(c, gl, 0);
     return false;

@@ -1666,7 +1666,25 @@ __device__ __forceinline__ void fused_select_row(float x, int col, bool valid, c
     __hip_atomic_store(F.pos, step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int MT, bool DIRECT, int EPI, bool LO, int PRO = PRO_NONE, bool SEL = false, int TAIL = TAIL_NONE>
+// int8 weights (GemmArgs::Wq): the MFMA B fragment of one k32 step from the lane's eight bytes
+// (a: k 0-3, b: k 4-7), each byte u = q + 128.  The fp16 with bits 0x6400 | u is 1024 + u, and
+// (1024 + u) - 1152 = q is exact in fp16, so the MFMAs see fp16(q) as they do from the fp16 copy.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ h16x8 q8_frag(unsigned a, unsigned b) {
+    auto two = [](unsigned x) {  // bytes 0, 1 of x -> the fp16 pair (q0, q1)
+        const unsigned bits = (x & 0xffu) | ((x & 0xff00u) << 8) | 0x64006400u;
+        return __builtin_bit_cast(h16x2, bits) - h16x2{(h16)1152.f, (h16)1152.f};
+    };
+    const h16x4 lo = __builtin_shufflevector(two(a), two(a >> 16), 0, 1, 2, 3);
+    const h16x4 hi = __builtin_shufflevector(two(b), two(b >> 16), 0, 1, 2, 3);
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// WQ (int8 weights, GemmArgs::wscale): 0 float16 weights; 1 the fp16(q) copy is streamed (W / Wf)
+// and every accumulator is multiplied by its column's multiplier before it leaves; 2 the same with
+// the int8 fragment copy (GemmArgs::Wq) streamed instead: half the weight bytes, the same MFMA
+// inputs and order, so the same bits as 1.
+template <int MT, bool DIRECT, int EPI, bool LO, int PRO = PRO_NONE, bool SEL = false, int TAIL = TAIL_NONE, int WQ = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEL ? 4 : 1, 8))) void gemm_skinny_kernel(GemmArgs g, int kc, float* __restrict__ part, ProArgs pa) {
     // Workgroup = 64 columns x one kc-deep K range; wave = 16 columns.  The
     // activation rows (M <= 64) of each CKK-deep K chunk are staged ONCE per
@@ -1685,6 +1703,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEL ? 4 : 1
     // or the GELU reduce of this workgroup's K range (PRO_GELU).  The MFMA order is the
     // plain kernel's, so both paths give identical results.
     static_assert(PRO == PRO_NONE || (MT == 1 && LO), "the prologue serves <= 8 hi/lo rows");
+    static_assert(WQ == 0 || (TAIL == TAIL_NONE && LO), "int8 weights: hi/lo rows, no last-arriver tail");
     // k32 steps per chunk; >= 32 hi/lo rows use 64-deep chunks: the two A buffers of 32
     // rows are then 16 KiB, so a workgroup fits beside another lane's encoder GEMM
     // workgroup (which leaves 30 KiB of the CU's LDS free, tools/coresidency_probe.hip)
@@ -1740,6 +1759,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEL ? 4 : 1
         wrow = g.W + (int64_t)n * g.ldw + k0 + 8 * (lane >> 4);
         wss = 32;
     }
+    // WQ == 2: this lane's 16 B per pair of k32 steps, 1 KB contiguous per wave (GemmArgs::Wq)
+    const uint8_t* wq = nullptr;
+    if constexpr (WQ == 2) {
+        const int blk = min(nb, ((g.N + 15) & ~15) - 16) >> 4;
+        wq = (const uint8_t*)g.Wq + (((int64_t)blk * (g.K >> 6) + (k0 >> 6)) * 64 + lane) * 16;
+    }
+    // WQ: this lane's column multiplier, loaded in the shadow of the weight stream
+    float wsc = 1.f;
+    if constexpr (WQ != 0) wsc = g.wscale[min(nb + (lane & 15), g.N - 1)];
+    // an accumulator as it leaves the kernel: fp32(acc * multiplier), rounded before any bias is
+    // added (the opaque move keeps the multiply out of a fused multiply-add)
+    auto leave = [&](float a) {
+        if constexpr (WQ != 0) {
+            a *= wsc;
+            asm("" : "+v"(a));
+        }
+        return a;
+    };
     SelPre sel_pre{};
     if constexpr (SEL) sel_pre = sel_preload(pa.sel, nb + (lane & 15));
     const int nsteps = kc / 32;  // multiple of 4
@@ -1770,7 +1807,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEL ? 4 : 1
                                                  (OSW_LDS void*)&As[buf][im][RPP * j * CKK], 16, 0, 0);
             }
     };
-    auto loadW = [&](h16x8 (&wf)[CK], int c) {
+    // weight registers (16 B each) per chunk: one per k32 step, int8 one per pair of steps (CK is even)
+    using WReg = std::conditional_t<WQ == 2, u32x4, h16x8>;
+    constexpr int WPC = WQ == 2 ? CK / 2 : CK;
+    static_assert(CK % 2 == 0, "int8 fragments come in pairs of k32 steps");
+    auto loadW = [&](WReg (&wf)[WPC], int c) {
+        if constexpr (WQ == 2) {
+#pragma unroll
+            for (int u = 0; u < WPC; ++u)
+                wf[u] = *(const u32x4*)(wq + (int64_t)1024 * min(c * WPC + u, nsteps / 2 - 1));
+        } else
 #pragma unroll
         for (int u = 0; u < CK; ++u) {
             const int st = min(c * CK + u, nsteps - 1);
@@ -1783,13 +1829,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEL ? 4 : 1
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int li = lane & 15, gq = lane >> 4;
-    auto consume = [&](const h16x8 (&wf)[CK], int buf, int c) {
+    auto consume = [&](const WReg (&wf)[WPC], int buf, int c) {
         const int steps = min(CK, nsteps - c * CK);
         // a short last chunk was staged from kc-CKK: its k32 steps sit at the end of the image
         const int shift = (c * CKK > kc - CKK && kc >= CKK) ? (c * CKK - (kc - CKK)) / 32 : 0;
 #pragma unroll
         for (int u = 0; u < CK; ++u) {
             if (u >= steps) break;
+            h16x8 wv;  // int8: converted right before its MFMAs
+            if constexpr (WQ == 2) wv = q8_frag(wf[u >> 1][2 * (u & 1)], wf[u >> 1][2 * (u & 1) + 1]);
+            else wv = wf[u];
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 const int row = mt * 16 + li;
@@ -1806,12 +1855,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEL ? 4 : 1
                     af = *(const h16x8*)&As[buf][0][row * CKK + ch * 8];
                     if constexpr (LO) al = *(const h16x8*)&As[buf][NIMG - 1][row * CKK + ch * 8];
                 }
-                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, wf[u], acc[mt], 0, 0, 0);
-                if constexpr (LO) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, wf[u], acc[mt], 0, 0, 0);
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, wv, acc[mt], 0, 0, 0);
+                if constexpr (LO) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, wv, acc[mt], 0, 0, 0);
             }
         }
     };
-    constexpr int INFLIGHT = CK + (PRO ? 0 : NIMG * APIECES);  // one chunk's loads per lane
+    constexpr int INFLIGHT = WPC + (PRO ? 0 : NIMG * APIECES);  // one chunk's loads per lane
     // 32-row hi/lo groups stream 64-deep chunks (CK = 2): one chunk of weights ahead is
     // 8 KB in flight per workgroup, so the 32 KB of a 256-deep K range took ~4 dependent
     // HBM round trips.  With preload_w every k32 step's weights (8 x 16 B per lane, 32
@@ -1820,7 +1869,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEL ? 4 : 1
         constexpr int WALL = 8;
         if (g.preload_w && nsteps <= WALL) {
             constexpr int AL = NIMG * APIECES;   // LDS-DMA loads per lane per chunk
-            h16x8 w[WALL];
+            constexpr int WREGS = WQ == 2 ? WALL / 2 : WALL;
+            WReg w[WREGS];
+            if constexpr (WQ == 2) {
+#pragma unroll
+                for (int u = 0; u < WREGS; ++u) w[u] = *(const u32x4*)(wq + (int64_t)1024 * min(u, nsteps / 2 - 1));
+            } else
 #pragma unroll
             for (int u = 0; u < WALL; ++u) w[u] = *(const h16x8*)(wrow + (int64_t)wss * min(u, nsteps - 1));
             stageA(0, 0);
@@ -1831,9 +1885,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEL ? 4 : 1
                 if (c + 1 < nch) wait_vmcnt<AL>();   // chunk c's A landed (and every weight load)
                 else wait_vmcnt<0>();
                 __builtin_amdgcn_s_barrier();
-                h16x8 wf[CK];
+                WReg wf[WPC];
 #pragma unroll
-                for (int u = 0; u < CK; ++u) wf[u] = w[c * CK + u];
+                for (int u = 0; u < WPC; ++u) wf[u] = w[c * WPC + u];
                 consume(wf, c & 1, c);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
@@ -1843,7 +1897,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEL ? 4 : 1
         }
     }
     {
-    h16x8 wa[CK], wb[CK];
+    WReg wa[WPC], wb[WPC];
     loadW(wa, 0);
     stageA(0, 0);
     // the fused-selection logits GEMM (5 chunks): the second chunk goes out before the
@@ -1864,8 +1918,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEL ? 4 : 1
         constexpr int KBIG = SEL ? 8 : 24;
         // (early residual loads where the VGPRs allow: not in the selecting logits GEMM, not
         // beside 24 slabs)
-        if (pa.ln.ks <= 8) resln_rows<PRO_ROWS, 8, !SEL>(pa.ln, 0, g.M, wx, pred, put);
-        else resln_rows<PRO_ROWS, KBIG, false>(pa.ln, 0, g.M, wx, pred, put);
+        // (the int8 logits GEMM never embeds: the entry is compiled out of it, see resln_rows; the
+        // float16 forms take a float16 table only, launch_gemm_skinny_pro checks)
+        constexpr int EMB = WQ == 0 ? EMB_F16 : DIRECT ? EMB_NONE : EMB_ANY;
+        if (pa.ln.ks <= 8) resln_rows<PRO_ROWS, 8, !SEL, EMB>(pa.ln, 0, g.M, wx, pred, put);
+        else resln_rows<PRO_ROWS, KBIG, false, EMB>(pa.ln, 0, g.M, wx, pred, put);
         __syncthreads();
     } else if constexpr (PRO == PRO_GELU) {
         const int64_t slab = (int64_t)g.M * g.K;
@@ -1919,8 +1976,9 @@ store:
     if constexpr (SEL) {
         static_assert(MT == 1 && DIRECT, "the fused selection serves the batch-1 logits GEMM");
         const bool valid = gq == 0 && col < g.N;
-        if (valid) __hip_atomic_store((float*)g.C + col, acc[0][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fused_select_row(acc[0][0], col, valid, pa.sel, sel_pre);
+        const float x = leave(acc[0][0]);  // the logit the finaliser reads back is the one selected on
+        if (valid) __hip_atomic_store((float*)g.C + col, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        fused_select_row(x, col, valid, pa.sel, sel_pre);
         return;
     }
     if (col < g.N) {
@@ -1930,12 +1988,12 @@ store:
             for (int i = 0; i < 4; ++i) {
                 const int m = mb + mt * 16 + gq * 4 + i;
                 if (m >= g.M) continue;
-                if constexpr (DIRECT) store_one<EPI>(g, m, col, acc[mt][i]);
+                if constexpr (DIRECT) store_one<EPI>(g, m, col, leave(acc[mt][i]));
                 // slabs are written through L2 (device-scope stores): no dirty lines left for
                 // the kernel-boundary write-back to drain before the consumer can start.  (Staging
                 // the tile through LDS for 8-B coalesced stores, as gemm_wide_kernel does, cost
                 // more in barriers than it saved: 7.7 -> 8.3 us at 64 rows, measured.)
-                else __hip_atomic_store(&part[((int64_t)ks * g.M + m) * g.N + col], acc[mt][i], __ATOMIC_RELAXED,
+                else __hip_atomic_store(&part[((int64_t)ks * g.M + m) * g.N + col], leave(acc[mt][i]), __ATOMIC_RELAXED,
                                         __HIP_MEMORY_SCOPE_AGENT);
             }
     }
@@ -2032,7 +2090,9 @@ constexpr int WBM = 64, WBN = 128, WSL = 3;
 template <int WN>
 constexpr int wide_lds(bool lo) { return (lo ? 2 * 2 : WSL) * WBM * BK * 2 + WSL * WN * BK * 2; }
 
-template <bool LO, int WN = WBN>
+// WS (int8 weights): W is the fp16(q) copy, staged as ever; the epilogue multiplies every
+// accumulator by its column's multiplier (GemmArgs::wscale), rounds, then adds the bias.
+template <bool LO, int WN = WBN, bool WS = false>
 __global__ __launch_bounds__(WN * 2, WN == WBN ? 2 : 1) void gemm_wide_kernel(GemmArgs g) {
     constexpr int NIMG = LO ? 2 : 1;
     constexpr int ASL = LO ? 2 : WSL;  // A ring slots
@@ -2152,6 +2212,11 @@ __global__ __launch_bounds__(WN * 2, WN == WBN ? 2 : 1) void gemm_wide_kernel(Ge
     constexpr int TS = WN + 2;  // LDS row stride (floats) of the 64 x WN tile
     static_assert(WBM * TS * 4 <= WSL * WN * BK * 2, "the tile fits the W ring");
     float* T = (float*)lw;
+    float ws[2] = {1.f, 1.f};  // WS: the multipliers of this lane's two columns, loaded once
+    (void)ws;
+    if constexpr (WS)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) ws[ni] = g.wscale[min(n0 + wave * 32 + ni * 16 + (lane & 15), g.N - 1)];
     __syncthreads();
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
@@ -2162,7 +2227,12 @@ __global__ __launch_bounds__(WN * 2, WN == WBN ? 2 : 1) void gemm_wide_kernel(Ge
             for (int ni = 0; ni < 2; ++ni) {
                 const int col = wave * 32 + ni * 16 + (lane & 15);
                 const int n = min(n0 + col, g.N - 1);
-                T[row * TS + col] = bias ? acc[mi][ni][i] + bias[n] : acc[mi][ni][i];
+                float v = acc[mi][ni][i];
+                if constexpr (WS) {
+                    v *= ws[ni];
+                    asm("" : "+v"(v));  // rounded to fp32 before the bias: no fused multiply-add
+                }
+                T[row * TS + col] = bias ? v + bias[n] : v;
             }
         }
     __syncthreads();
@@ -2182,11 +2252,11 @@ __global__ __launch_bounds__(WN * 2, WN == WBN ? 2 : 1) void gemm_wide_kernel(Ge
     }
 }
 
-template <bool LO>
+template <bool LO, bool WS = false>
 void launch_wide256(const GemmArgs& g, int ks, hipStream_t s) {
     constexpr int lds = wide_lds<256>(LO);
-    set_lds_once((const void*)gemm_wide_kernel<LO, 256>, lds);
-    gemm_wide_kernel<LO, 256><<<dim3((g.N + 255) / 256, (g.M + WBM - 1) / WBM, ks), 512, lds, s>>>(g);
+    set_lds_once((const void*)gemm_wide_kernel<LO, 256, WS>, lds);
+    gemm_wide_kernel<LO, 256, WS><<<dim3((g.N + 255) / 256, (g.M + WBM - 1) / WBM, ks), 512, lds, s>>>(g);
 }
 
 void launch_wide(const GemmArgs& g, int ks, hipStream_t s) {
@@ -2194,13 +2264,16 @@ void launch_wide(const GemmArgs& g, int ks, hipStream_t s) {
     // OSW_WIDE256_ALL=1 (A/B switch): the split-K projections of beam rows on it as well
     static const bool n128 = getenv("OSW_WIDE_N128") != nullptr;
     static const bool all256 = getenv("OSW_WIDE256_ALL") != nullptr;
+    if (g.wscale && !g.A_lo) throw std::invalid_argument("int8 weights: the wide GEMM serves hi/lo rows");
     if (!n128 && ((ks == 1 && g.kc == 0 && g.N >= 16384) || all256)) {
-        if (g.A_lo) launch_wide256<true>(g, ks, s);
+        if (g.wscale) launch_wide256<true, true>(g, ks, s);
+        else if (g.A_lo) launch_wide256<true>(g, ks, s);
         else launch_wide256<false>(g, ks, s);
         return;
     }
     const dim3 grid((g.N + WBN - 1) / WBN, (g.M + WBM - 1) / WBM, ks);
-    if (g.A_lo) gemm_wide_kernel<true><<<grid, 256, 0, s>>>(g);
+    if (g.wscale) gemm_wide_kernel<true, WBN, true><<<grid, 256, 0, s>>>(g);
+    else if (g.A_lo) gemm_wide_kernel<true><<<grid, 256, 0, s>>>(g);
     else gemm_wide_kernel<false><<<grid, 256, 0, s>>>(g);
 }
 
@@ -2214,10 +2287,36 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs g, int kspl
     }
 }
 
+// The int8-weight forms of the plain skinny kernel (GemmArgs::wscale; the int8 fragments when
+// GemmArgs::Wq is given, else the fp16(q) copy: the debug A/B of the two streams).  Refused, never
+// served in float16, where there is no such form.
+template <int MT, bool DIRECT>
+void skinny_q8(const GemmArgs& g, dim3 grid, int kc, float* part, hipStream_t s) {
+    if (!g.wscale || !g.A_lo || g.epi != EPI_F32)
+        throw std::invalid_argument("int8 weights: hi/lo rows, fp32 out and the row multipliers");
+    if (g.Wq) {
+        gemm_skinny_kernel<MT, DIRECT, EPI_F32, true, PRO_NONE, false, TAIL_NONE, 2><<<grid, 256, 0, s>>>(g, kc, part, ProArgs{});
+    } else if constexpr (MT <= 2) {
+        gemm_skinny_kernel<MT, DIRECT, EPI_F32, true, PRO_NONE, false, TAIL_NONE, 1><<<grid, 256, 0, s>>>(g, kc, part, ProArgs{});
+    } else {
+        throw std::invalid_argument("int8 weights: more than 32 rows stream the int8 fragments (GemmArgs::Wq)");
+    }
+}
+
 template <int MT, int EPI>
 void skinny_dispatch(const GemmArgs& g, int ksplit, float* part, hipStream_t s) {
     const dim3 grid((g.N + 63) / 64, ksplit);
     const int kc = g.K / ksplit;
+    if (g.wscale || g.Wq) {
+        if (ksplit == 1) {
+            skinny_q8<MT, true>(g, grid, kc, part, s);
+        } else {
+            skinny_q8<MT, false>(g, grid, kc, part, s);
+            const int64_t total = (int64_t)g.M * g.N;
+            splitk_reduce_kernel<EPI_F32><<<(unsigned)std::min<int64_t>((total + 255) / 256, 1024), 256, 0, s>>>(g, ksplit, part);
+        }
+        return;
+    }
     if (ksplit == 1) {
         if (g.A_lo) gemm_skinny_kernel<MT, true, EPI, true><<<grid, 256, 0, s>>>(g, kc, part, ProArgs{});
         else gemm_skinny_kernel<MT, true, EPI, false><<<grid, 256, 0, s>>>(g, kc, part, ProArgs{});
@@ -2282,6 +2381,12 @@ int launch_gemm_skinny_partial(const GemmArgs& g0, float* part, hipStream_t s) {
         if (g.A_lo) gemm_skinny_kernel<MT_, false, EPI_F32, true><<<grid, 256, 0, s>>>(g, kc, part, ProArgs{}); \
         else gemm_skinny_kernel<MT_, false, EPI_F32, false><<<grid, 256, 0, s>>>(g, kc, part, ProArgs{}); \
     } while (0)
+    if (g.wscale || g.Wq) {  // hi/lo rows: groups of at most 32
+        if (!g.A_lo) throw std::invalid_argument("int8 weights: the skinny GEMM serves hi/lo rows");
+        if (std::min(g.M, gr) <= 16) skinny_q8<1, false>(g, grid, kc, part, s);
+        else skinny_q8<2, false>(g, grid, kc, part, s);
+        return ks;
+    }
     switch (std::min(g.M, gr) <= 16 ? 1 : std::min(g.M, gr) <= 32 ? 2 : std::min(g.M, gr) <= 48 ? 3 : 4) {
         case 1: OSW_SKINNY_PART(1); break;
         case 2: OSW_SKINNY_PART(2); break;
@@ -2306,6 +2411,7 @@ int launch_gemm_skinny_gelu_tail(const GemmArgs& g0, float* part, const ProArgs&
     const dim3 grid = g.pair_rows ? dim3((unsigned)(8 * ((units + 7) / 8) * nz), 1, 1)
                                   : dim3((g.N + 63) / 64, ks, nz);
     const int kc = g.K / ks;
+    if (g.wscale || g.Wq) throw std::invalid_argument("GELU tail (OSW_GELU_TAIL): not with int8 weights");
     if (!g.A_lo || g.M > 64 || g.N % 64)
         throw std::invalid_argument("GELU tail: hi/lo operand, <= 64 rows, N a multiple of 64");
     switch (std::min(g.M, gr) <= 16 ? 1 : 2) {
@@ -2333,10 +2439,27 @@ int launch_gemm_skinny_pro(const GemmArgs& g0, int pro, const ProArgs& pa, bool 
     g.preload_w = wb_late ? 0 : 1;
     if (pro == PRO_GELU ? g.M > GELU_ROWS || kc > GELU_KC : g.M > PRO_ROWS)
         throw std::invalid_argument("fused GEMM prologue: rows or K range exceed its LDS image");
+    const bool q8 = g.wscale || g.Wq;  // int8 weights: the prologue forms stream the int8 fragments
+    if (pro == PRO_RESLN && !pa.ln.part && pa.ln.tok_scale && !q8)
+        throw std::invalid_argument("int8 token embedding feeding a float16 qkv matrix in the fused step: "
+                                    "quantise dec.l0.qkv.w too, or neither");
+    if (pro == PRO_RESLN && !pa.ln.part && q8 && direct)
+        throw std::invalid_argument("int8 weights: the direct (logits) form has no embedding entry");
+    if (q8 && !(g.wscale && g.Wq)) throw std::invalid_argument("int8 weights: fused prologue needs Wq and wscale");
+    if (q8 && attn_tail) throw std::invalid_argument("attention tail (OSW_B1_ATTN_TAIL): not with int8 weights");
+    if (q8 && direct && pro != PRO_RESLN) throw std::invalid_argument("int8 weights: no direct GELU-prologue form");
     if (select) {
         if (!direct || pro != PRO_RESLN || g.M != 1 || g.epi != EPI_F32 || g.ldc != g.N)
             throw std::invalid_argument("fused selection: batch-1 logits GEMM only");
+        if (q8) gemm_skinny_kernel<1, true, EPI_F32, true, PRO_RESLN, true, TAIL_NONE, 2><<<grid, 256, 0, s>>>(g, kc, part, pa);
+        else
         gemm_skinny_kernel<1, true, EPI_F32, true, PRO_RESLN, true><<<grid, 256, 0, s>>>(g, kc, part, pa);
+        return ks;
+    }
+    if (q8) {
+        if (direct) gemm_skinny_kernel<1, true, EPI_F32, true, PRO_RESLN, false, TAIL_NONE, 2><<<grid, 256, 0, s>>>(g, kc, part, pa);
+        else if (pro == PRO_RESLN) gemm_skinny_kernel<1, false, EPI_F32, true, PRO_RESLN, false, TAIL_NONE, 2><<<grid, 256, 0, s>>>(g, kc, part, pa);
+        else gemm_skinny_kernel<1, false, EPI_F32, true, PRO_GELU, false, TAIL_NONE, 2><<<grid, 256, 0, s>>>(g, kc, part, pa);
         return ks;
     }
     if (attn_tail) {
@@ -2375,6 +2498,33 @@ __global__ __launch_bounds__(256) void frag_pack_kernel(const h16* __restrict__ 
 void launch_frag_pack(const h16* W, int64_t ldw, int N, int K, h16* Wf, hipStream_t s) {
     const int64_t pieces = (int64_t)((N + 15) / 16) * (K / 32) * 64;
     frag_pack_kernel<<<(unsigned)((pieces + 255) / 256), 256, 0, s>>>(W, ldw, N, K, Wf, pieces);
+}
+
+// one thread per 16-B piece of Wq: piece p = (blk * K/64 + j) * 64 + lane holds column
+// blk*16 + (lane & 15), k = 64 j + 8 (lane >> 4) + [0, 8) in bytes 0-7 and those k + 32 in bytes
+// 8-15, each as q + 128 (= q ^ 0x80 on the two's-complement byte); q = 0 past N
+__global__ __launch_bounds__(256) void frag_pack_q8_kernel(const int8_t* __restrict__ q, int N, int K,
+                                                           int8_t* __restrict__ Wq, int64_t pieces) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= pieces) return;
+    const int lane = (int)(p & 63);
+    const int64_t t = p >> 6;
+    const int kp = K >> 6;
+    const int j = (int)(t % kp);
+    const int n = (int)(t / kp) * 16 + (lane & 15);
+    const int k = j * 64 + 8 * (lane >> 4);
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (n < N) {
+        const uint2 a = *(const uint2*)(q + (int64_t)n * K + k), b = *(const uint2*)(q + (int64_t)n * K + k + 32);
+        v = u32x4{a.x, a.y, b.x, b.y};
+    }
+    *(u32x4*)(Wq + p * 16) = v ^ 0x80808080u;
+}
+
+void launch_frag_pack_q8(const int8_t* q, int N, int K, int8_t* Wq, hipStream_t s) {
+    if (K % 64) throw std::invalid_argument("int8 fragments: K a multiple of 64");
+    const int64_t pieces = (int64_t)((N + 15) / 16) * (K / 64) * 64;
+    frag_pack_q8_kernel<<<(unsigned)((pieces + 255) / 256), 256, 0, s>>>(q, N, K, Wq, pieces);
 }
 
 int tiled_ksplit(int M, int N, int K) {
@@ -2435,6 +2585,7 @@ void prepare_gemm_kernels() {
         set_lds_once((const void*)gemm8p_kernel<EPI_F16_GELU, 2>, l8p);
         set_lds_once((const void*)gemm_wide_kernel<true, 256>, wide_lds<256>(true));
         set_lds_once((const void*)gemm_wide_kernel<false, 256>, wide_lds<256>(false));
+        set_lds_once((const void*)gemm_wide_kernel<true, 256, true>, wide_lds<256>(true));
     });
 }
 
@@ -2448,6 +2599,8 @@ void launch_gemm_variant(const GemmArgs& g, int variant, hipStream_t s) {
     static const bool no_wide = getenv("OSW_NO_WIDE") != nullptr;  // A/B switch
     const bool wide_ok = g.epi == EPI_F32 && g.kc == 0 && g.c_grp_rows == g.M && g.K % BK == 0 &&
                          (g.M <= WBM || g.A_lo);
+    if (g.wscale && !(wide_ok && g.A_lo && (variant == 0 || variant == 5)))
+        throw std::invalid_argument("int8 weights: served by the decoder's skinny and wide GEMMs only");
     if (wide_ok && (variant == 5 || (variant == 0 && (g.A_lo || (g.N >= 16384 && !no_wide))))) {
         launch_wide(g, 1, s);
         return;

@@ -52,6 +52,7 @@ void resolve_events(osw_ctx* c) {
             case CL_ENC_ATTN: p.enc_attn_ms += ms; p.enc_attn_launches++; p.enc_attn_flops += e.work; break;
             case CL_MEL: p.mel_kernel_ms += ms; p.mel_kernel_launches++; p.mel_kernel_bytes += e.work; break;
             case CL_XATTN: p.xattn_ms += ms; p.xattn_launches++; p.xattn_bytes += e.work; break;
+            case CL_LOGITS: c->logits_ms += ms; c->logits_launches++; break;
             case CL_STAGE_MEL: p.mel_ms += ms; break;
             case CL_STAGE_ENC: p.encoder_ms += ms; break;
             case CL_STAGE_XKV: p.crosskv_ms += ms; break;
@@ -130,8 +131,13 @@ void build_weight_table(osw_ctx* c) {
         Tensor& t = c->w[n];
         t.frag_n = (int)N;
         t.frag_k = (int)K;
+        t.q8 = std::make_shared<std::atomic<int>>(0);
         add_tensor(c, n + ".frag", (N + 15) / 16 * 16 * K, true);
         c->w[n + ".frag"].set = true;  // derived: written by pack_frag
+        // the row multipliers of int8 weights (osw_set_weight_quant); the int8 fragments take half
+        // of the ".frag" region
+        add_tensor(c, n + ".scale", N, false);
+        c->w[n + ".scale"].set = true;
     };
     frag("dec.tok", d.n_vocab, Dd);
     for (int i = 0; i < d.n_text_layer; ++i) {
@@ -160,6 +166,7 @@ void build_weight_table(osw_ctx* c) {
         (void)hipFree(p);
         if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
     });
+    c->siblings = std::make_shared<std::atomic<int>>(0);
     char* arena = (char*)ap;
     HIPCHK(hipMemsetAsync(arena, 0, total, c->stream));
     size_t off = 0;
@@ -182,6 +189,42 @@ const h16* WFR(osw_ctx* c, const std::string& n) {
     if (off) return nullptr;
     auto it = c->w.find(n + ".frag");
     return it == c->w.end() ? nullptr : (const h16*)it->second.ptr;
+}
+bool is_q8(osw_ctx* c, const std::string& n) {
+    const Tensor& t = W(c, n);
+    return t.q8 && t.q8->load(std::memory_order_relaxed) != 0;
+}
+void gemm_weights(osw_ctx* c, const std::string& n, GemmArgs& g) {
+    g.W = WH(c, n);
+    g.ldw = g.K;
+    if (is_q8(c, n)) {  // the int8 fragments, whatever OSW_NO_WFRAG says: there is no float16 form of them
+        g.Wf = nullptr;
+        g.Wq = (const int8_t*)W(c, n + ".frag").ptr;
+        g.wscale = WF(c, n + ".scale");
+    } else {
+        g.Wf = WFR(c, n);
+    }
+}
+const float* tok_scale(osw_ctx* c) { return is_q8(c, "dec.tok") ? WF(c, "dec.tok.scale") : nullptr; }
+// The embedding is layer 0's qkv prologue in the one-row step, and the float16 prologues are
+// compiled without the embedding's multipliers: an int8 dec.tok needs an int8 dec.l0.qkv.w.  Checked
+// when the weights are finalized and at every decoder step (a matrix may be set again later), at
+// every row count, so the same weights never decode at one batch size and fail at another.
+void require_embedding_kind(osw_ctx* c) {
+    REQUIRE(!is_q8(c, "dec.tok") || is_q8(c, "dec.l0.qkv.w"),
+            "int8 dec.tok with a float16 dec.l0.qkv.w: quantise dec.l0.qkv.w too, or neither");
+}
+// A matrix changes between float16 and int8 only while nothing has its kind baked in: decode
+// graphs hold the kernels chosen at capture, and a sibling's graphs cannot be seen from here.
+void set_kind(osw_ctx* c, const std::string& n, Tensor& t, bool q8) {
+    if (!t.q8) {
+        REQUIRE(!q8, "tensor " + n + ": int8 weights are accepted for dec.tok and dec.lN.{qkv,o,xq,xo,fc1,fc2}.w");
+        return;
+    }
+    if ((t.q8->load() != 0) == q8) return;
+    REQUIRE(c->dgraphs.empty() && (!c->siblings || c->siblings->load() == 0),
+            "tensor " + n + ": float16 <-> int8 is refused once decode graphs or sibling contexts exist");
+    t.q8->store(q8 ? 1 : 0);
 }
 // rewrite the fragment-major copy after the matrix was written (on the context's stream)
 void pack_frag(osw_ctx* c, const std::string& n) {
@@ -1022,6 +1065,8 @@ int osw_create_sibling(osw_ctx* parent, int32_t max_batch, osw_ctx** out) {
         make_streams(c);
         c->w = parent->w;          // same device pointers
         c->arena = parent->arena;  // keeps the weights alive past the parent's destroy
+        c->siblings = parent->siblings;
+        if (c->siblings) c->siblings->fetch_add(1);
         c->baton = parent->baton;
         c->sibling = true;
         c->finalized = true;
@@ -1048,6 +1093,7 @@ int osw_destroy(osw_ctx* c) {
             for (void* p : c->owned) (void)hipFree(p);
             if (c->done_host) (void)hipHostFree(c->done_host);
             destroy_streams(c);
+            if (c->sibling && c->siblings) c->siblings->fetch_sub(1);
             c->arena.reset();
         }
         delete c;
@@ -1063,6 +1109,7 @@ int osw_set_weight(osw_ctx* c, const char* name, const void* host, int64_t nbyte
         GateLock gate_(capture_gate());  // weight upload (a model loading while another serves)
         Tensor& t = W(c, name);
         const std::string nm(name);
+        set_kind(c, nm, t, false);
         if (nm == "enc.conv1.w" && c->C1 != c->d.n_mels) {
             const int64_t De = c->d.n_audio_state, M = c->d.n_mels;
             REQUIRE(nbytes == De * 3 * M * 2, "enc.conv1.w: wrong byte count");
@@ -1080,6 +1127,48 @@ int osw_set_weight(osw_ctx* c, const char* name, const void* host, int64_t nbyte
         pack_frag(c, nm);
         HIPCHK(hipStreamSynchronize(c->stream));
         t.set = true;
+    });
+}
+
+int osw_set_weight_quant(osw_ctx* c, const char* name, const int8_t* q, const float* mult, int64_t n_q,
+                      int64_t n_mult) {
+    return guard([&] {
+        REQUIRE(c && name && q && mult, "null argument");
+        std::lock_guard<std::mutex> lk(c->mu);
+        REQUIRE(!c->sibling, "sibling contexts share their parent's weights (read-only)");
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        const std::string nm(name);
+        Tensor& t = W(c, nm);
+        REQUIRE(t.q8 && t.frag_n, "tensor " + nm + ": int8 weights are accepted for dec.tok and dec.lN.{qkv,o,xq,xo,fc1,fc2}.w");
+        REQUIRE(n_q == t.numel && n_mult == t.frag_n, "tensor " + nm + ": wrong element count");
+        const int N = t.frag_n, K = t.frag_k;
+        REQUIRE(K % 64 == 0, "tensor " + nm + ": int8 fragments need K a multiple of 64");
+        for (int n = 0; n < N; ++n) REQUIRE(std::isfinite(mult[n]), "tensor " + nm + ": a multiplier is not finite");
+        set_kind(c, nm, t, true);
+        std::vector<h16> half((size_t)t.numel);
+        for (size_t i = 0; i < half.size(); ++i) half[i] = (h16)(float)q[i];  // exact
+        std::vector<void*> tmp;
+        int8_t* dq = dalloc<int8_t>((size_t)t.numel, tmp);
+        HIPCHK(hipMemcpyAsync(t.ptr, half.data(), half.size() * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(W(c, nm + ".scale").ptr, mult, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dq, q, (size_t)t.numel, hipMemcpyHostToDevice, c->stream));
+        launch_frag_pack_q8(dq, N, K, (int8_t*)W(c, nm + ".frag").ptr, c->stream);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        dfree(dq, tmp);
+        HIPCHK(e);
+        t.set = true;
+    });
+}
+
+int osw_weight_is_quant(osw_ctx* c, const char* name, int32_t* out) {
+    return guard([&] {
+        REQUIRE(c && name && out, "null argument");
+        std::lock_guard<std::mutex> lk(c->mu);
+        const Tensor& t = W(c, name);
+        REQUIRE(t.q8, std::string("tensor ") + name + ": not a matrix that can hold int8 weights");
+        *out = t.q8->load() ? 1 : 0;
     });
 }
 
@@ -1105,6 +1194,7 @@ int osw_init_weight_uniform(osw_ctx* c, const char* name, uint64_t seed, int64_t
         Tensor& t = W(c, name);
         REQUIRE(!(std::string(name) == "enc.conv1.w" && c->C1 != c->d.n_mels),
                 "enc.conv1.w needs osw_set_weight when n_mels is not a multiple of 64");
+        set_kind(c, name, t, false);
         launch_init_uniform(t.ptr, t.f16, t.numel, hash_stream_key(seed, stream), scale, offset, zero_lo, zero_hi,
                             c->stream);
         HIPCHK(hipGetLastError());
@@ -1122,6 +1212,7 @@ int osw_finalize(osw_ctx* c) {
         for (auto& kv : c->w)
             if (!kv.second.set) missing += kv.first + " ";
         REQUIRE(missing.empty(), "missing tensors: " + missing);
+        require_embedding_kind(c);
         c->finalized = true;
     });
 }
@@ -1322,6 +1413,8 @@ int osw_set_profiling(osw_ctx* c, int32_t enable) {
         c->prof = enable != 0;
         c->prof_eager = enable == 2;
         c->pf = osw_profile{};
+        c->logits_ms = 0;
+        c->logits_launches = 0;
     });
 }
 

@@ -34,6 +34,9 @@ struct ResLnArgs {
     int D;
     int V;              // rows of tok_emb: an id outside [0, V) is clamped into it
     int pos_row;        // 1: row r's position is pos[r] (row refill), 0: every row's is pos[0]
+    // int8 token embedding (tok_emb holds fp16(q)): the multiplier of every row of tok_emb, so
+    // x' = fp32((float)tok_emb[t][c] * tok_scale[t]) + pos_emb[pos][c]; nullptr: float16
+    const float* tok_scale = nullptr;
 };
 
 // rows r0 .. r0+nr-1 (nr <= NR); emit(r, c, y) receives every LayerNorm output;
@@ -41,9 +44,17 @@ struct ResLnArgs {
 // loads per batch (the sums do not depend on it: the padding adds exact zeros).  EARLY:
 // the residual, bias, gain and shift are loaded ahead of the first slab batch (one round
 // trip fewer, ~15 more VGPRs); otherwise after the slabs / the statistics.  Same arithmetic.
-template <int NR, int KB, bool EARLY, class Emit>
+// EMB: what the embedding entry is compiled for.  EMB_F16: a float16 table (tok_scale is not
+// looked at: the float16 GEMM prologues, which compile to what they did before int8 weights
+// existed; the host refuses to hand them an int8 table).  EMB_ANY: a float16 table, or an int8
+// one with its multipliers (tok_scale) — the same statements either way.  EMB_NONE: the caller
+// never takes the entry (A.part is given), which is then not compiled in (the int8 logits GEMM
+// with the selection: its scalar registers are short).
+enum Emb : int { EMB_NONE = 0, EMB_F16 = 1, EMB_ANY = 2 };
+template <int NR, int KB, bool EARLY, int EMB = EMB_F16, class Emit>
 __device__ __forceinline__ void resln_rows(const ResLnArgs& A, int r0, int nr, bool write_x, float* red, Emit emit) {
 #pragma clang fp contract(off)
+    const bool slabs = EMB == EMB_NONE || A.part != nullptr;
     const int t = threadIdx.x, w = t >> 6, l = t & 63;
     const int D = A.D;
     const bool h4 = 4 * t < D, h1 = 1024 + t < D;
@@ -73,7 +84,7 @@ __device__ __forceinline__ void resln_rows(const ResLnArgs& A, int r0, int nr, b
     };
     if constexpr (EARLY) {
         load_gb();
-        if (A.part) load_x();
+        if (slabs) load_x();
     }
     float v[NR][5];
 #pragma unroll
@@ -84,7 +95,7 @@ __device__ __forceinline__ void resln_rows(const ResLnArgs& A, int r0, int nr, b
         const int64_t rb = (int64_t)(r0 + r) * D;
         f32x4 a4;
         float a1;
-        if (A.part) {
+        if (slabs) {
             f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
             float s1 = 0.f;
             for (int k0 = 0; k0 < A.ks; k0 += KB) {
@@ -118,8 +129,16 @@ __device__ __forceinline__ void resln_rows(const ResLnArgs& A, int r0, int nr, b
             const h16x4 e4 = *(const h16x4*)(A.tok_emb + (int64_t)tk * D + c4);
             const int pos = min(A.pos[A.pos_row ? r0 + r : 0], A.ctx - 1);
             const float* pe = A.pos_emb + (int64_t)pos * D;
-            a4 = f32x4{(float)e4[0], (float)e4[1], (float)e4[2], (float)e4[3]} + *(const f32x4*)(pe + c4);
-            a1 = (float)A.tok_emb[(int64_t)tk * D + c1] + pe[c1];
+            f32x4 t4 = f32x4{(float)e4[0], (float)e4[1], (float)e4[2], (float)e4[3]};
+            float t1 = (float)A.tok_emb[(int64_t)tk * D + c1];
+            if constexpr (EMB == EMB_ANY)
+                if (A.tok_scale) {  // the product is rounded to fp32, then the add (contraction is off)
+                    const float ws = A.tok_scale[tk];
+                    t4 *= ws;
+                    t1 *= ws;
+                }
+            a4 = t4 + *(const f32x4*)(pe + c4);
+            a1 = t1 + pe[c1];
         }
         if (write_x) {
             if (h4) *(f32x4*)(A.x_out + rb + c4) = a4;

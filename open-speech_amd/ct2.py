@@ -15,7 +15,9 @@ real file is unverified):
     str = u16 length (incl. NUL) | utf-8 bytes | NUL
 
 dtype ids: 0 float32, 1 int8, 2 int16, 3 int32, 4 float16, 5 bfloat16.  int8 weights
-carry a per-row ``<name>_scale`` (float32) variable; they are dequantised here.
+carry a per-row ``<name>_scale`` (float32) variable; they are dequantised here, except that
+``ct2_to_canonical(..., keep_int8=True)`` hands the decoder matrices the int8 kernels serve over
+as stored (``weights.QuantizedMatrix``: the file's bytes and ``1 / scale``).
 
 Variable names (CTranslate2 ``WhisperSpec`` as produced by its transformers
 converter): ``encoder/conv1/weight`` ``[D, n_mels, 3]``; ``encoder/layer_i/
@@ -31,7 +33,7 @@ import struct
 import numpy as np
 
 from .dims import WhisperDims
-from .weights import crop_positional
+from .weights import QuantizedMatrix, crop_positional
 
 _DT = {0: np.float32, 1: np.int8, 2: np.int16, 3: np.int32, 4: np.float16}
 _DT_ID = {np.dtype(np.float32): 0, np.dtype(np.int8): 1, np.dtype(np.int16): 2, np.dtype(np.int32): 3,
@@ -143,9 +145,31 @@ def dims_from_ct2(v: dict) -> WhisperDims:
                        n_text_state=D, n_text_head=D // 64, n_text_layer=n_dec)
 
 
-def ct2_to_canonical(v: dict, aliases: dict, d: WhisperDims) -> dict:
+def _get_q8(v: dict, aliases: dict, name: str):
+    """The variable as stored when it is int8 with a ``_scale`` (neither dequantised nor re-quantised:
+    the file's bytes, multiplier 1 / scale per row), else None."""
+    name = aliases.get(name, name)
+    x, sc = v.get(name), v.get(name + "_scale")
+    if x is None or sc is None or x.dtype != np.int8 or x.ndim != 2:
+        return None
+    sc = np.asarray(sc, np.float32).reshape(-1)
+    if sc.shape != (x.shape[0],):
+        raise ValueError(f"{name}_scale has {sc.size} entries for {x.shape[0]} rows")
+    return QuantizedMatrix(np.ascontiguousarray(x), (np.float32(1.0) / sc).astype(np.float32))
+
+
+def ct2_to_canonical(v: dict, aliases: dict, d: WhisperDims, keep_int8: bool = False) -> dict:
+    """keep_int8: the decoder matrices with int8 kernels (dec.tok, dec.lN.{qkv,o,xq,xo,fc1,fc2}.w) that
+    the file stores as int8 come back as ``QuantizedMatrix``.  None of them is fused or permuted on
+    the way to the canonical layout, so row n's multiplier stays row n's.  Everything else, the
+    encoder and the fused cross-K/V projection included, is dequantised as ever."""
     g = lambda n: _get(v, aliases, n)  # noqa: E731
     h16 = lambda a: np.ascontiguousarray(a, dtype=np.float16)  # noqa: E731
+
+    def dm(n):  # a decoder matrix the int8 kernels serve
+        q = _get_q8(v, aliases, n) if keep_int8 else None
+        return q if q is not None else h16(g(n))
+
     f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
     w = {}
     w["enc.conv1.w"] = h16(g("encoder/conv1/weight").transpose(0, 2, 1))
@@ -169,30 +193,30 @@ def ct2_to_canonical(v: dict, aliases: dict, d: WhisperDims) -> dict:
         w[p + ".fc2.b"] = f32(g(f"{q}/ffn/linear_1/bias"))
     w["enc.lnpost.g"] = f32(g("encoder/layer_norm/gamma"))
     w["enc.lnpost.b"] = f32(g("encoder/layer_norm/beta"))
-    w["dec.tok"] = h16(g("decoder/embeddings/weight"))
+    w["dec.tok"] = dm("decoder/embeddings/weight")
     w["dec.pos"] = f32(g("decoder/position_encodings/encodings"))
     kv, kvb = [], []
     for i in range(d.n_text_layer):
         p, q = f"dec.l{i}", f"decoder/layer_{i}"
         w[p + ".ln1.g"] = f32(g(f"{q}/self_attention/layer_norm/gamma"))
         w[p + ".ln1.b"] = f32(g(f"{q}/self_attention/layer_norm/beta"))
-        w[p + ".qkv.w"] = h16(g(f"{q}/self_attention/linear_0/weight"))
+        w[p + ".qkv.w"] = dm(f"{q}/self_attention/linear_0/weight")
         w[p + ".qkv.b"] = f32(g(f"{q}/self_attention/linear_0/bias"))
-        w[p + ".o.w"] = h16(g(f"{q}/self_attention/linear_1/weight"))
+        w[p + ".o.w"] = dm(f"{q}/self_attention/linear_1/weight")
         w[p + ".o.b"] = f32(g(f"{q}/self_attention/linear_1/bias"))
         w[p + ".ln2.g"] = f32(g(f"{q}/attention/layer_norm/gamma"))
         w[p + ".ln2.b"] = f32(g(f"{q}/attention/layer_norm/beta"))
-        w[p + ".xq.w"] = h16(g(f"{q}/attention/linear_0/weight"))
+        w[p + ".xq.w"] = dm(f"{q}/attention/linear_0/weight")
         w[p + ".xq.b"] = f32(g(f"{q}/attention/linear_0/bias"))
         kv.append(g(f"{q}/attention/linear_1/weight"))
         kvb.append(g(f"{q}/attention/linear_1/bias"))
-        w[p + ".xo.w"] = h16(g(f"{q}/attention/linear_2/weight"))
+        w[p + ".xo.w"] = dm(f"{q}/attention/linear_2/weight")
         w[p + ".xo.b"] = f32(g(f"{q}/attention/linear_2/bias"))
         w[p + ".ln3.g"] = f32(g(f"{q}/ffn/layer_norm/gamma"))
         w[p + ".ln3.b"] = f32(g(f"{q}/ffn/layer_norm/beta"))
-        w[p + ".fc1.w"] = h16(g(f"{q}/ffn/linear_0/weight"))
+        w[p + ".fc1.w"] = dm(f"{q}/ffn/linear_0/weight")
         w[p + ".fc1.b"] = f32(g(f"{q}/ffn/linear_0/bias"))
-        w[p + ".fc2.w"] = h16(g(f"{q}/ffn/linear_1/weight"))
+        w[p + ".fc2.w"] = dm(f"{q}/ffn/linear_1/weight")
         w[p + ".fc2.b"] = f32(g(f"{q}/ffn/linear_1/bias"))
     w["dec.crosskv.w"] = h16(np.concatenate(kv))
     w["dec.crosskv.b"] = f32(np.concatenate(kvb))

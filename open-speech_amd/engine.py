@@ -143,9 +143,35 @@ class WhisperEngine:
                    f"osw_get_weight({name})")
         return out
 
+    def set_weight_q8(self, name: str, q: np.ndarray, mult: np.ndarray) -> None:
+        """Int8 weights for one decoder matrix (osw_set_weight_quant): W[n][k] ~ q[n][k] * mult[n], q int8
+        [N][K], mult float32 [N].  Accepted for dec.tok and dec.lN.{qkv,o,xq,xo,fc1,fc2}.w."""
+        q = np.asarray(q)
+        mult = np.asarray(mult)
+        if q.dtype != np.int8 or q.ndim != 2 or mult.shape != (q.shape[0],):
+            raise ValueError(f"{name}: q int8 [N][K] and mult [N] expected, got {q.dtype} {q.shape} / {mult.shape}")
+        q = np.ascontiguousarray(q)
+        m = np.ascontiguousarray(mult, dtype=np.float32)
+        _lib.check(self.lib.osw_set_weight_quant(self.ctx, name.encode(), q.ctypes.data_as(C.c_void_p),
+                                              m.ctypes.data_as(C.POINTER(C.c_float)), q.size, m.size),
+                   f"osw_set_weight_quant({name})")
+
+    def weight_is_q8(self, name: str) -> bool:
+        """Whether decoder matrix ``name`` holds int8 weights; a name that cannot raises OswError."""
+        out = C.c_int32()
+        _lib.check(self.lib.osw_weight_is_quant(self.ctx, name.encode(), C.byref(out)), f"osw_weight_is_quant({name})")
+        return bool(out.value)
+
     def load_weights(self, w: dict) -> None:
+        """Upload every canonical tensor; a ``weights.QuantizedMatrix`` value goes through set_weight_q8."""
+        from .weights import QuantizedMatrix
         for sp in canonical_specs(self.dims):
             arr = w[sp.name]
+            if isinstance(arr, QuantizedMatrix):
+                if tuple(arr.q.shape) != tuple(sp.shape):
+                    raise ValueError(f"{sp.name}: int8 shape {arr.q.shape}, expected {sp.shape}")
+                self.set_weight_q8(sp.name, arr.q, arr.mult)
+                continue
             want = np.float16 if sp.dtype == F16 else np.float32
             self.set_weight(sp.name, np.asarray(arr, dtype=want))
         _lib.check(self.lib.osw_finalize(self.ctx), "osw_finalize")
@@ -673,6 +699,56 @@ class WhisperEngine:
                                                int(bool(use_wf)), raw.ctypes.data_as(C.POINTER(C.c_float)), raw.size,
                                                C.byref(ks)), "osw_debug_dec_gemm")
         return self._guarded(raw, (M, N) if form == 2 else (ks.value, M, N))
+
+    def debug_dec_gemm_q8(self, form: int, A_hi: np.ndarray, A_lo: np.ndarray, q: np.ndarray, mult: np.ndarray,
+                          use_q8_stream: bool = True) -> np.ndarray:
+        """debug_dec_gemm on int8 weights (osw_debug_dec_gemm_quant): q int8 [N][K], mult float32 [N].
+        use_q8_stream: the skinny kernel streams the int8 fragments; else the fp16(q) copy with the
+        multipliers through the same launcher.  Forms 3 / 4 (the opt-in tails) are refused."""
+        A_hi = np.ascontiguousarray(A_hi, dtype=np.float16)
+        lo = np.ascontiguousarray(A_lo, dtype=np.float16)
+        q = np.asarray(q)
+        if q.dtype != np.int8:
+            raise ValueError("q must be int8")
+        q = np.ascontiguousarray(q)
+        m = np.ascontiguousarray(mult, dtype=np.float32)
+        M, K = A_hi.shape
+        N = q.shape[0]
+        if q.shape != (N, K) or lo.shape != (M, K) or m.shape != (N,):
+            raise ValueError("shapes: A_hi, A_lo [M][K], q [N][K], mult [N]")
+        raw = np.empty((1 if form == 2 else max(K // 64, 1)) * M * N + self.DEBUG_GUARD, np.float32)
+        ks = C.c_int32()
+        vp = C.c_void_p
+        _lib.check(self.lib.osw_debug_dec_gemm_quant(self.ctx, int(form), M, N, K, A_hi.ctypes.data_as(vp),
+                                                  lo.ctypes.data_as(vp), q.ctypes.data_as(vp),
+                                                  m.ctypes.data_as(C.POINTER(C.c_float)), int(bool(use_q8_stream)),
+                                                  raw.ctypes.data_as(C.POINTER(C.c_float)), raw.size, C.byref(ks)),
+                   "osw_debug_dec_gemm_quant")
+        return self._guarded(raw, (M, N) if form == 2 else (ks.value, M, N))
+
+    def debug_dec_gemm_time(self, A_hi, A_lo, q, mult, copies: int = 1, warm: int = 20, launches: int = 200):
+        """Per-launch microseconds of the skinny split-K projection with float16 and with int8 weights,
+        alternating (osw_debug_dec_gemm_time) -> (us_f16 [launches], us_q8 [launches])."""
+        A_hi = np.ascontiguousarray(A_hi, dtype=np.float16)
+        lo = np.ascontiguousarray(A_lo, dtype=np.float16)
+        q = np.ascontiguousarray(q, dtype=np.int8)
+        m = np.ascontiguousarray(mult, dtype=np.float32)
+        (M, K), N = A_hi.shape, q.shape[0]
+        if q.shape != (N, K) or lo.shape != (M, K) or m.shape != (N,):
+            raise ValueError("shapes: A_hi, A_lo [M][K], q [N][K], mult [N]")
+        a, b = np.zeros(launches, np.float32), np.zeros(launches, np.float32)
+        vp, fp = C.c_void_p, C.POINTER(C.c_float)
+        _lib.check(self.lib.osw_debug_dec_gemm_time(self.ctx, M, N, K, A_hi.ctypes.data_as(vp), lo.ctypes.data_as(vp),
+                                                    q.ctypes.data_as(vp), m.ctypes.data_as(fp), int(copies), int(warm),
+                                                    int(launches), a.ctypes.data_as(fp), b.ctypes.data_as(fp)),
+                   "osw_debug_dec_gemm_time")
+        return a, b
+
+    def debug_logits_profile(self):
+        """(ms, launches) of the fused step's logits GEMM since set_profiling(True, eager_decode=True)."""
+        ms, n = C.c_double(), C.c_int64()
+        _lib.check(self.lib.osw_debug_logits_profile(self.ctx, C.byref(ms), C.byref(n)), "osw_debug_logits_profile")
+        return ms.value, n.value
 
     def debug_dec_resln(self, x, gain, shift, slabs=None, bias=None, embed=None, W=None, direct: bool = False,
                         use_wf: bool = False):

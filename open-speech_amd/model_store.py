@@ -125,16 +125,34 @@ def alignment_heads(src: ModelSource) -> list | None:
     return None
 
 
-def load_weights(src: ModelSource) -> dict | None:
-    """Canonical weights for a resolved source (None for random init)."""
+INT8_COMPUTE_TYPES = ("int8_float16", "int8")
+
+
+def int8_decoder(compute_type: str | None) -> bool:
+    """Whether ``STT_COMPUTE_TYPE`` asks for int8 decoder weights.  ``int8`` means what
+    ``int8_float16`` means here: the activations stay float16 pairs on this backend either way."""
+    return (compute_type or "").strip().lower() in INT8_COMPUTE_TYPES
+
+
+def load_weights(src: ModelSource, compute_type: str | None = None) -> dict | None:
+    """Canonical weights for a resolved source (None for random init).  compute_type ``int8_float16``
+    / ``int8``: the decoder matrices come back as ``weights.QuantizedMatrix`` — a CTranslate2 file's
+    stored int8 as it is, float checkpoints quantised per row at load, as CTranslate2 does.  Anything
+    else, or None: float16, exactly as before."""
+    q8 = int8_decoder(compute_type)
+    w = None
     if src.kind == "hf":
-        return load_hf_weights(src)
-    if src.kind == "ct2":
+        w = load_hf_weights(src)
+    elif src.kind == "ct2":
         from .ct2 import ct2_to_canonical, read_model_bin
 
         v, aliases = read_model_bin(os.path.join(src.path, "model.bin"))
-        return ct2_to_canonical(v, aliases, src.dims)
-    return None
+        w = ct2_to_canonical(v, aliases, src.dims, keep_int8=True) if q8 else ct2_to_canonical(v, aliases, src.dims)
+    if w is not None and q8:
+        from .weights import quantize_decoder
+
+        w = quantize_decoder(w, src.dims)
+    return w
 
 
 def load_hf_weights(src: ModelSource) -> dict:

@@ -230,6 +230,52 @@ def crop_positional(table: np.ndarray, d: WhisperDims) -> np.ndarray:
     return np.ascontiguousarray(table[:d.n_audio_ctx], dtype=np.float32)
 
 
+# ---- int8 decoder weights (STT_COMPUTE_TYPE=int8_float16) ----
+@dataclass
+class QuantizedMatrix:
+    """W[n][k] ~ q[n][k] * mult[n]: q int8 [N][K], mult float32 [N] (engine.load_weights sends it through
+    set_weight_q8).  CTranslate2 stores ``scale = 1 / mult``."""
+    q: np.ndarray
+    mult: np.ndarray
+
+    def dequantize(self) -> np.ndarray:
+        """float32 q * mult, each product rounded once: the matrix the int8 kernels multiply by, up
+        to their single rounding of acc * mult."""
+        return self.q.astype(np.float32) * self.mult.astype(np.float32)[:, None]
+
+
+def q8_names(d: WhisperDims) -> list[str]:
+    """The decoder matrices that have int8 kernels (the seven kinds the skinny GEMM streams)."""
+    return ["dec.tok"] + [f"dec.l{i}.{k}.w" for i in range(d.n_text_layer) for k in ("qkv", "o", "xq", "xo", "fc1", "fc2")]
+
+
+def quantize_rows(w: np.ndarray) -> QuantizedMatrix:
+    """CTranslate2's per-row int8 rule restated: scale = 127 / max|row|, q = clip(rint(w * scale), -127,
+    127), mult = 1 / scale in float32; an all-zero row gets q = 0, mult = 1.  The arithmetic is float32
+    and ``rint`` rounds half to even: CTranslate2's own rounding mode here is unpinned (its kernels
+    differ by ISA), so a value exactly between two steps may land one step away from its choice."""
+    w = np.asarray(w, dtype=np.float32)
+    if w.ndim != 2:
+        raise ValueError("quantize_rows takes a matrix [N][K]")
+    amax = np.abs(w).max(axis=1)
+    zero = amax == 0
+    scale = np.where(zero, np.float32(1.0), np.float32(127.0) / np.where(zero, np.float32(1.0), amax)).astype(np.float32)
+    q = np.clip(np.rint(w * scale[:, None]), -127, 127).astype(np.int8)
+    mult = (np.float32(1.0) / scale).astype(np.float32)
+    return QuantizedMatrix(q, mult)
+
+
+def quantize_decoder(w: dict, d: WhisperDims) -> dict:
+    """The canonical weights with every decoder matrix of q8_names quantised by quantize_rows (what
+    CTranslate2 does to a float checkpoint loaded with compute_type int8*); one already quantised
+    is kept as stored."""
+    out = dict(w)
+    for n in q8_names(d):
+        if not isinstance(out[n], QuantizedMatrix):
+            out[n] = quantize_rows(np.asarray(out[n], dtype=np.float32))
+    return out
+
+
 def make_tensor(spec: TensorSpec, d: WhisperDims, seed: int, stream: int) -> np.ndarray:
     shape = spec_shape(spec, d)
     if spec.kind == "sinusoid":
