@@ -471,6 +471,53 @@ int osw_debug_history_rules(osw_ctx* ctx, float* logits, int32_t rows, int32_t V
 int osw_debug_history_rules_time(osw_ctx* ctx, int32_t rows, int32_t V, int32_t n_hist, float repetition_penalty,
                                  int32_t no_repeat_ngram_size, int32_t iters, float* us);
 
+/* One selection step (launch_select and, for beam_size > 1, launch_beam: exactly what a decode
+ * step launches after its logits GEMM, plus the history rules when the options turn them on) on
+ * caller-supplied logits and state, for the per-kernel tests (tests/test_gpu_select.py).  The
+ * entry builds the decode plan of `mode` from `opts` (seed included; token_budget is taken from
+ * io->budget), binds it to the context's own buffers, uploads the state, launches, and copies
+ * every in/out array back.  The arrival and ticket counters are the context's own and are NOT
+ * reset: `counters` returns them as the launch left them (all zero, or the next call misbehaves).
+ * SelState travels as 10 32-bit words per row {n_sampled, last, penult, last_ts, done, lang,
+ * sum_lp (float), nsp (float), plen, n_lp}, BeamWin as 6 per window {n_hyp, best_len, done,
+ * best_nlp, best_norm (float), best_raw (float)}.  Every *_len is the array's size in elements
+ * (words); an array the mode does not use may be NULL with length 0.
+ * OSW_EINVAL, before any launch, for whatever could make a kernel index out of bounds: rows not a
+ * multiple of the group (beam_size, or best_of when sampling) or above the row capacity, windows
+ * above max_batch, a step counter outside [0, n_text_ctx), n_sampled outside [0, max_tok], a
+ * sampling row whose counter is not plen - 1 + n_sampled, plen out of range (sessions; 0
+ * elsewhere), a prompt or history token outside [0, V) other than the -1 language placeholder,
+ * rows of one beam window that differ in n_sampled / plen / done / counter, an ancestry entry
+ * outside the window's rows, max_tok or pstride that are not the plan's, an undersized array, or
+ * an open session. */
+#define OSW_SELECT_BATCH 0
+#define OSW_SELECT_REFILL 1
+#define OSW_SELECT_SESSION 2
+typedef struct osw_select_io {
+    int32_t mode;      /* OSW_SELECT_* */
+    int32_t n_prefix;  /* batch: prompt positions before <|startoftranscript|> */
+    int32_t rows;      /* decoder rows: windows x group */
+    int32_t max_tok;   /* ints per row of tokens / best_tok: max(1, max_length - prompt length) */
+    int32_t pstride;   /* ints per row of prompt: the prompt length (sessions: n_text_ctx) */
+    int64_t logits_len, pos_len, state_len, prompt_len, cur_tok_len, tokens_len, budget_len, anc_len, bwin_len,
+        best_tok_len, lp_hist_len, best_lp_len, lang_probs_len, counters_len;
+    float* logits;         /* [rows][V]; copied back only with a history rule on */
+    int32_t* pos;          /* batch: [1] the shared step counter, else [rows]; in/out */
+    int32_t* state;        /* [rows][10]; in/out */
+    const int32_t* prompt; /* [rows][pstride] */
+    int32_t* cur_tok;      /* [rows]; in/out */
+    int32_t* tokens;       /* [rows][max_tok]; in/out */
+    const int32_t* budget; /* [rows] or NULL: no budgets (sessions: zeros) */
+    int32_t* anc;          /* beam: [rows][n_text_ctx]; in/out */
+    int32_t* bwin;         /* beam: [windows][6]; in/out */
+    int32_t* best_tok;     /* beam: [windows][max_tok]; in/out */
+    float* lp_hist;        /* confidences on: [rows][n_text_ctx]; in/out */
+    float* best_lp;        /* confidences on, beam: [windows][n_text_ctx]; in/out */
+    float* lang_probs;     /* confidences on, multilingual: [windows][n_langs]; in/out */
+    int32_t* counters;     /* out: [1 + rows] rows finalised, then each row's slice tickets */
+} osw_select_io;
+int osw_debug_select_step(osw_ctx* ctx, const osw_decode_opts* opts, const osw_select_io* io);
+
 /* Parity helper: one encoder block on x [T][D] fp32 (host), result to y (host). */
 int osw_encoder_layer_debug(osw_ctx* ctx, int32_t layer, const float* x, float* y, int32_t T);
 

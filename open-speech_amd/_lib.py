@@ -70,6 +70,19 @@ class osw_enc_gemm_desc(C.Structure):
                  ("heads_slot", C.POINTER(C.c_int32)), ("C", C.c_void_p)])
 
 
+_SELECT_ARRAYS = ("logits", "pos", "state", "prompt", "cur_tok", "tokens", "budget", "anc", "bwin", "best_tok",
+                  "lp_hist", "best_lp", "lang_probs", "counters")
+_SELECT_FLOAT = ("logits", "lp_hist", "best_lp", "lang_probs")
+
+
+class osw_select_io(C.Structure):
+    """osw_debug_select_step's arrays: every ``*_len`` counts 32-bit words (include/osw.h)."""
+    ARRAYS, FLOAT = _SELECT_ARRAYS, _SELECT_FLOAT
+    _fields_ = ([(n, C.c_int32) for n in ("mode", "n_prefix", "rows", "max_tok", "pstride")] +
+                [(n + "_len", C.c_int64) for n in _SELECT_ARRAYS] +
+                [(n, C.POINTER(C.c_float if n in _SELECT_FLOAT else C.c_int32)) for n in _SELECT_ARRAYS])
+
+
 class osw_profile(C.Structure):
     _fields_ = [("mel_ms", C.c_double), ("encoder_ms", C.c_double), ("crosskv_ms", C.c_double),
                 ("decoder_ms", C.c_double), ("total_ms", C.c_double), ("decode_steps", C.c_int64),
@@ -134,6 +147,8 @@ _SIGS = {
                                           P(C.c_int32), C.c_float, C.c_int32]),
     "osw_debug_history_rules_time": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
                                                C.c_int32, P(C.c_float)]),
+    # one selection step (select kernel + beam update) on host logits and state (tests/test_gpu_select.py)
+    "osw_debug_select_step": (C.c_int, [C.c_void_p, P(osw_decode_opts), P(osw_select_io)]),
     "osw_encoder_layer_debug": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_float), C.c_int32]),
     "osw_debug_gemm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                  P(C.c_float), C.c_int32, P(C.c_float)]),

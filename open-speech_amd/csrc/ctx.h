@@ -415,6 +415,7 @@ struct Readback {
     std::vector<float> cum, lang;
 };
 void bind_plan(osw_ctx* c, DecodePlan& p, const osw_decode_opts* o);
+void plan_select(osw_ctx* c, const DecodePlan& p, int rows, int windows);
 void run_chunk(osw_ctx* c, const DecodePlan& p, int rows, int windows, int CH, bool graph,
                const SelFuse* sf = nullptr);
 std::vector<int> finished_windows(osw_ctx* c, const DecodePlan& p, int rows, int windows,

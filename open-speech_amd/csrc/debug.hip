@@ -142,6 +142,142 @@ int osw_debug_history_rules_time(osw_ctx* c, int32_t rows, int32_t V, int32_t n_
     });
 }
 
+// One selection step on host state (osw.h osw_debug_select_step): the plan the decode paths
+// build, bound to the context's buffers, one plan_select.  Everything a kernel indexes with is
+// checked here first; the row modes restate select.h sel_mode on the host.
+int osw_debug_select_step(osw_ctx* c, const osw_decode_opts* o, const osw_select_io* io) {
+    return guard([&] {
+        static_assert(sizeof(SelState) == 40 && sizeof(BeamWin) == 24, "the word layouts osw.h documents");
+        REQUIRE(c && o && io, "null argument");
+        REQUIRE(io->mode >= OSW_SELECT_BATCH && io->mode <= OSW_SELECT_SESSION, "select step: unknown mode");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        REQUIRE(!c->sess, "select step: a decode session is open");
+        const osw_dims& d = c->d;
+        const int V = d.n_vocab, ctx = d.n_text_ctx;
+        const DecodeMode mode = io->mode == OSW_SELECT_BATCH    ? DecodeMode::Batch
+                                : io->mode == OSW_SELECT_REFILL ? DecodeMode::Refill
+                                                                : DecodeMode::Session;
+        // the caller's prompts carry the prefix contents; the plan needs only their count
+        osw_decode_opts oo = *o;
+        oo.n_prefix = mode == DecodeMode::Batch ? io->n_prefix : 0;
+        oo.prefix_tokens = io->prompt;
+        oo.token_budget = io->budget;
+        oo.language_tokens = nullptr;
+        DecodePlan plan(mode, &oo, d, oo.n_prefix);
+        const SelParams& sp = plan.sp;
+        const int rows = io->rows, group = plan.group, K = plan.beam, max_tok = plan.max_tok, pstride = sp.pstride;
+        REQUIRE(rows >= 1 && rows % group == 0 && rows <= c->R, "select step: rows must be a multiple of the group, at most the row capacity");
+        const int windows = rows / group;
+        REQUIRE(windows <= c->B, "select step: more windows than max_batch");
+        REQUIRE(io->max_tok == max_tok && io->pstride == pstride, "select step: max_tok / pstride are not the plan's");
+        REQUIRE(K == 1 || ctx <= 448, "select step: beam rows hold at most 448 positions");
+        REQUIRE(sp.eot >= 0 && sp.eot < V && sp.no_speech >= 0 && sp.no_speech < V && sp.tb >= 0 && sp.tb <= V,
+                "select step: special token outside the vocabulary");
+        REQUIRE(sp.first_lang >= 0 && sp.n_langs >= 0 && sp.first_lang + sp.n_langs <= V && sp.n_langs <= LANG_CAP &&
+                    (plan.ss.english || sp.n_langs >= 1),
+                "select step: language token range");
+        const bool per_row = sp.pos_row != 0, beam = K > 1, conf = c->conf;
+        const bool langp = conf && !plan.ss.english;
+        const int64_t n_pos = per_row ? rows : 1;
+        auto need = [&](const void* p, int64_t len, int64_t want, const char* what) {
+            if (!(p && len >= want)) throw OswError(OSW_EINVAL, std::string("select step: undersized array: ") + what);
+        };
+        need(io->logits, io->logits_len, (int64_t)rows * V, "logits");
+        need(io->pos, io->pos_len, n_pos, "pos");
+        need(io->state, io->state_len, (int64_t)rows * 10, "state");
+        need(io->prompt, io->prompt_len, (int64_t)rows * pstride, "prompt");
+        need(io->cur_tok, io->cur_tok_len, rows, "cur_tok");
+        need(io->tokens, io->tokens_len, (int64_t)rows * max_tok, "tokens");
+        need(io->counters, io->counters_len, 1 + rows, "counters");
+        if (io->budget) need(io->budget, io->budget_len, rows, "budget");
+        if (beam) {
+            need(io->anc, io->anc_len, (int64_t)rows * ctx, "anc");
+            need(io->bwin, io->bwin_len, (int64_t)windows * 6, "bwin");
+            need(io->best_tok, io->best_tok_len, (int64_t)windows * max_tok, "best_tok");
+        }
+        if (conf) need(io->lp_hist, io->lp_hist_len, (int64_t)rows * ctx, "lp_hist");
+        if (conf && beam) need(io->best_lp, io->best_lp_len, (int64_t)windows * ctx, "best_lp");
+        if (langp) need(io->lang_probs, io->lang_probs_len, (int64_t)windows * sp.n_langs, "lang_probs");
+        const SelState* st = (const SelState*)io->state;
+        for (int r = 0; r < rows; ++r) {
+            const SelState& s = st[r];
+            const int step = io->pos[per_row ? r : 0];
+            REQUIRE(step >= 0 && step < ctx, "select step: step counter outside [0, n_text_ctx)");
+            if (mode == DecodeMode::Session)
+                REQUIRE(s.plen >= sp.tail && s.plen < sp.max_length && s.plen <= pstride, "select step: plen out of range");
+            else
+                REQUIRE(s.plen == 0, "select step: plen is a session row's");
+            const int pl = row_plen(sp, s), sot = pl - sp.tail;
+            REQUIRE(s.n_sampled >= 0 && s.n_sampled <= max_tok, "select step: n_sampled outside [0, max_tok]");
+            REQUIRE(s.lang >= 0 && s.lang < V, "select step: language outside the vocabulary");
+            for (int i = 0; i < pl; ++i) {
+                const int t = io->prompt[(size_t)r * pstride + i];
+                REQUIRE((t >= 0 && t < V) || (t == -1 && !plan.ss.english && i == sot + 1),
+                        "select step: prompt token outside the vocabulary");
+            }
+            for (int i = 0; i < s.n_sampled; ++i) {
+                const int t = io->tokens[(size_t)r * max_tok + i];
+                REQUIRE(t >= 0 && t < V, "select step: history token outside the vocabulary");
+            }
+            // (select.h sel_mode) a row past its prompt and not done samples
+            if (step >= pl - 1 && !s.done)
+                REQUIRE(step == pl - 1 + s.n_sampled, "select step: a sampling row's counter is not plen - 1 + n_sampled");
+            if (!beam) continue;
+            const int r0 = r - r % K;
+            const SelState& s0 = st[r0];
+            REQUIRE(s.n_sampled == s0.n_sampled && s.plen == s0.plen && (s.done != 0) == (s0.done != 0) &&
+                        step == io->pos[per_row ? r0 : 0],
+                    "select step: rows of one beam window differ in n_sampled / plen / done / counter");
+            for (int p = 0; p < step; ++p) {
+                const int a = io->anc[(size_t)r * ctx + p];
+                REQUIRE(a >= r0 && a < r0 + K, "select step: ancestry entry outside the window's rows");
+            }
+        }
+        // the state up, one selection, everything back
+        bind_plan(c, plan, &oo);
+        auto up = [&](void* dst, const void* src, int64_t words) {
+            HIPCHK(hipMemcpyAsync(dst, src, (size_t)words * 4, hipMemcpyHostToDevice, c->stream));
+        };
+        auto down = [&](void* dst, const void* src, int64_t words) {
+            HIPCHK(hipMemcpyAsync(dst, src, (size_t)words * 4, hipMemcpyDeviceToHost, c->stream));
+        };
+        up(c->logits, io->logits, (int64_t)rows * V);
+        up(c->pos, io->pos, n_pos);
+        up(c->sel, io->state, (int64_t)rows * 10);
+        up(c->prompt, io->prompt, (int64_t)rows * pstride);
+        up(c->cur_tok, io->cur_tok, rows);
+        up(c->tokens, io->tokens, (int64_t)rows * max_tok);
+        if (io->budget) up(c->budget, io->budget, rows);
+        else HIPCHK(hipMemsetAsync(c->budget, 0, (size_t)rows * 4, c->stream));
+        if (beam) {
+            up(c->anc, io->anc, (int64_t)rows * ctx);
+            up(c->bwin, io->bwin, (int64_t)windows * 6);
+            up(c->btok, io->best_tok, (int64_t)windows * max_tok);
+        }
+        if (conf) up(c->lp_hist, io->lp_hist, (int64_t)rows * ctx);
+        if (conf && beam) up(c->best_lp, io->best_lp, (int64_t)windows * ctx);
+        if (langp) up(c->lang_probs, io->lang_probs, (int64_t)windows * sp.n_langs);
+        plan_select(c, plan, rows, windows);
+        HIPCHK(hipGetLastError());
+        if (plan.hr.on) down(io->logits, c->logits, (int64_t)rows * V);
+        down(io->pos, c->pos, n_pos);
+        down(io->state, c->sel, (int64_t)rows * 10);
+        down(io->cur_tok, c->cur_tok, rows);
+        down(io->tokens, c->tokens, (int64_t)rows * max_tok);
+        if (beam) {
+            down(io->anc, c->anc, (int64_t)rows * ctx);
+            down(io->bwin, c->bwin, (int64_t)windows * 6);
+            down(io->best_tok, c->btok, (int64_t)windows * max_tok);
+        }
+        if (conf) down(io->lp_hist, c->lp_hist, (int64_t)rows * ctx);
+        if (conf && beam) down(io->best_lp, c->best_lp, (int64_t)windows * ctx);
+        if (langp) down(io->lang_probs, c->lang_probs, (int64_t)windows * sp.n_langs);
+        down(io->counters, c->sel_arrive, 1 + rows);
+        HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
 int osw_encoder_layer_debug(osw_ctx* c, int32_t layer, const float* x, float* y, int32_t T) {
     return guard([&] {
         REQUIRE(c && x && y, "null argument");

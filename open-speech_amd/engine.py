@@ -92,6 +92,13 @@ class Alignment:
     token_prob: np.ndarray    # [n] softmax(logits[:eot])[token]
 
 
+# csrc/seltypes.h SelState / BeamWin as numpy records (debug_select_step)
+SEL_STATE = np.dtype([("n_sampled", "i4"), ("last", "i4"), ("penult", "i4"), ("last_ts", "i4"), ("done", "i4"),
+                      ("lang", "i4"), ("sum_lp", "f4"), ("nsp", "f4"), ("plen", "i4"), ("n_lp", "i4")])
+BEAM_WIN = np.dtype([("n_hyp", "i4"), ("best_len", "i4"), ("done", "i4"), ("best_nlp", "i4"), ("best_norm", "f4"),
+                     ("best_raw", "f4")])
+
+
 def _i32p(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
@@ -541,6 +548,46 @@ class WhisperEngine:
                                                     float(repetition_penalty), int(no_repeat_ngram_size)),
                    "osw_debug_history_rules")
         return x
+
+    SELECT_MODES = {"batch": 0, "refill": 1, "session": 2}
+
+    def debug_select_step(self, cfg: DecodeConfig, state: dict, mode: str = "batch", n_prefix: int = 0) -> dict:
+        """One selection step (select kernel, and the beam update for ``cfg.beam_size`` > 1) on the
+        caller's logits and state (osw_debug_select_step).  ``state`` maps the names of
+        ``_lib.osw_select_io.ARRAYS`` to arrays: ``logits`` [rows][V], ``pos`` [1] or [rows],
+        ``state`` [rows] of ``SEL_STATE``, ``prompt`` [rows][pstride], ``cur_tok`` [rows], ``tokens``
+        [rows][max_tok], optionally ``budget`` [rows]; beam: ``anc`` [rows][n_text_ctx], ``bwin``
+        [windows] of ``BEAM_WIN``, ``best_tok`` [windows][max_tok]; with ``cfg.confidences``
+        ``lp_hist``, ``best_lp``, ``lang_probs``.  Returns copies as the step left them, plus
+        ``counters`` (the context's arrival and ticket counters); the input is not changed."""
+        self._set_confidences(cfg.confidences)
+        cfg = dataclasses.replace(cfg, token_budget=None)
+        o, keep = self._opts(cfg, 0, None)
+        out = {}
+        io = _lib.osw_select_io()
+        for name in _lib.osw_select_io.ARRAYS:
+            a = state.get(name)
+            if name == "counters":
+                a = np.full(1 + len(state["state"]), -1, np.int32)
+            if a is None:
+                continue
+            if name in ("state", "bwin"):
+                a = np.array(a, dtype=SEL_STATE if name == "state" else BEAM_WIN, order="C")
+                words = a.view(np.int32)
+            else:
+                a = np.array(a, dtype=np.float32 if name in _lib.osw_select_io.FLOAT else np.int32, order="C")
+                words = a
+            out[name] = a
+            setattr(io, name, words.ctypes.data_as(type(getattr(io, name))))
+            setattr(io, name + "_len", words.size)
+        io.mode = self.SELECT_MODES[mode]
+        io.n_prefix = int(n_prefix)
+        io.rows = len(out["state"])
+        io.max_tok = out["tokens"].shape[1]
+        io.pstride = out["prompt"].shape[1]
+        _lib.check(self.lib.osw_debug_select_step(self.ctx, C.byref(o), C.byref(io)), "osw_debug_select_step")
+        del keep
+        return out
 
     def debug_history_rules_time(self, rows: int, n_hist: int, repetition_penalty: float = 1.0,
                                  no_repeat_ngram_size: int = 0, iters: int = 200) -> float:
