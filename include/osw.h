@@ -36,6 +36,8 @@
  *                 transcribe without it (src/backends/faster_whisper.py:235-246)
  *   osw_get_alignment_matrix / osw_debug_dtw
  *       stage-level read-back and the DTW kernel alone, used only by the parity tests
+ *   osw_debug_align_post / osw_debug_align_tail / osw_debug_align_self_attn / osw_debug_align_scores
+ *       one launch of the alignment pass's other kernels on host data, used only by the parity tests
  *   osw_debug_enc_attn / osw_debug_dec_xattn / osw_debug_dec_self_attn
  *       one attention launch on host data, used only by the parity tests
  *   osw_debug_dec_gemm / osw_debug_dec_gemm_quant / osw_debug_dec_resln / osw_debug_dec_gelu
@@ -456,6 +458,50 @@ int osw_get_alignment_matrix(osw_ctx* ctx, int32_t window, float* out, int64_t o
  * openai-whisper timing.dtw / transformers' _dynamic_time_warping for the parity tests. */
 int osw_debug_dtw(osw_ctx* ctx, const float* x, int32_t T, int32_t F, int32_t* text_idx, int32_t* time_idx,
                   int32_t* len);
+
+/* ---- the other alignment kernels, one production launcher per call on host data (parity tests:
+ * tests/test_gpu_align_kernels.py; references: tests/align_kernels_ref.py) ----
+ * Like the attention calls below: temporary device buffers, exactly one call of the launcher the
+ * alignment pass uses on the context's stream, the results copied back.  Shapes are arguments and
+ * do not depend on the context's dims (head width 64; positions <= 448).  Whatever could make a
+ * kernel index out of bounds is OSW_EINVAL before any launch.  Pure outputs are filled with 0xff
+ * bytes (a NaN pattern) before the launch, so an unwritten element and a stray store both show;
+ * in/out arrays come back as the launch left them.  They replace no reference interface: the
+ * reference runs these steps inside CTranslate2 Whisper::align [upstream].
+ *
+ * launch_align_post: scores fp32 [n_slots][n_heads][pstride][TK] (raw scaled scores; rows p >= len
+ * are never read) -> stats [n_slots][n_heads][pstride][2] (row max, sum of exp over all TK keys),
+ * colstats [n_slots][n_heads][TK][2] (mean and population std over positions 0 .. len - 1 of the
+ * probabilities of frames < frames[slot]), M [n_slots][pstride][TK] (rows 0 .. len - head - 2,
+ * frames < frames[slot]).  OSW_EINVAL: pstride % 16 != 0 or > 448, len > pstride, len < head + 2,
+ * frames outside [1, TK], an even width or one above 15, head not 1 or 3. */
+int osw_debug_align_post(osw_ctx* ctx, const float* scores, int32_t n_slots, int32_t n_heads, int32_t pstride,
+                         int32_t TK, const int32_t* len, const int32_t* head, const int32_t* frames,
+                         const int32_t* width, float* stats, float* colstats, float* M);
+/* launch_align_tail at position pos: logits fp32 [rows][V], forced [rows][ctx], per row slot (-1:
+ * not aligned; else distinct, < n_slots), len (<= ctx) and head (1 or 3).  In/out: token_logprob
+ * [n_slots][ctx], cur_tok [rows], done [rows] (packed into and unpacked from the kernel's row
+ * state).  OSW_EINVAL: eot outside [1, V], ctx > 448, a forced token outside [0, V). */
+int osw_debug_align_tail(osw_ctx* ctx, const float* logits, int32_t rows, int32_t V, int32_t eot, int32_t ctx_len,
+                         int32_t pos, const int32_t* slot, const int32_t* len, const int32_t* head,
+                         const int32_t* forced, int32_t n_slots, float* token_logprob, int32_t* cur_tok,
+                         int32_t* done);
+/* launch_align_self_attn at position pos (clamped to ctx_len - 1 by the kernel): qkv_slabs fp32
+ * [ks][rows][3 D], D = 64 H, bias [3 D], done [rows] (a row with done != 0 is skipped).  In/out:
+ * the fp32 caches kcache, vcache [rows][H][ctx_len][64].  out fp32 [rows][D] = the kernel's fp16
+ * hi + lo pair, summed (NaN where nothing was written).  OSW_EINVAL: ctx_len > 448, pos < 0. */
+int osw_debug_align_self_attn(osw_ctx* ctx, const float* qkv_slabs, int32_t ks, const float* bias, float* kcache,
+                              float* vcache, int32_t rows, int32_t H, int32_t ctx_len, int32_t pos,
+                              const int32_t* done, float* out);
+/* launch_align_scores at position pos: q_slabs fp32 [ks][rows][D], D = 64 H, bias [D] or NULL, K
+ * fp16 [rows][H][T][64], layer_heads n_layer_heads pairs {head < H, head_idx < n_heads} with
+ * distinct head_idx, per row slot (-1 or distinct, < n_slots) and len (<= pstride).  In/out:
+ * scores fp32 [n_slots][n_heads][pstride][T]; a row with slot >= 0 and pos < len writes row pos
+ * of each listed head_idx. */
+int osw_debug_align_scores(osw_ctx* ctx, const float* q_slabs, int32_t ks, const float* bias, const void* K,
+                           int32_t rows, int32_t H, int32_t T, const int32_t* layer_heads, int32_t n_layer_heads,
+                           int32_t n_heads, int32_t pos, const int32_t* slot, const int32_t* len, int32_t pstride,
+                           int32_t n_slots, float* scores);
 
 /* The history-rules kernel alone (osw_decode_opts::repetition_penalty / no_repeat_ngram_size) on
  * host data: logits [rows][V] in and out, row r's history tokens[r * stride .. + n_hist[r]).

@@ -142,6 +142,19 @@ _SIGS = {
                                            P(C.c_int32)]),
     "osw_debug_dtw": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, C.c_int32, P(C.c_int32), P(C.c_int32),
                                 P(C.c_int32)]),
+    # the alignment pass's other kernels, one production launcher per call (tests/test_gpu_align_kernels.py)
+    "osw_debug_align_post": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_float),
+                                       P(C.c_float), P(C.c_float)]),
+    "osw_debug_align_tail": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32), C.c_int32,
+                                       P(C.c_float), P(C.c_int32), P(C.c_int32)]),
+    "osw_debug_align_self_attn": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, P(C.c_float), P(C.c_float),
+                                            P(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int32),
+                                            P(C.c_float)]),
+    "osw_debug_align_scores": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, P(C.c_float), C.c_void_p, C.c_int32,
+                                         C.c_int32, C.c_int32, P(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                         P(C.c_int32), P(C.c_int32), C.c_int32, C.c_int32, P(C.c_float)]),
     # the history-rules kernel alone (replaces ctranslate2's RepetitionPenalty / NoRepeatNgram processors)
     "osw_debug_history_rules": (C.c_int, [C.c_void_p, P(C.c_float), C.c_int32, C.c_int32, P(C.c_int32), C.c_int32,
                                           P(C.c_int32), C.c_float, C.c_int32]),

@@ -215,7 +215,10 @@ __global__ __launch_bounds__(256) void align_colstats_kernel(const float* __rest
     colstats[o + 1] = sqrtf(var / (float)P);
 }
 
-// median of the W normalised weights around frame f (reflect padding), W odd
+// median of the W normalised weights around frame f (reflect padding), W odd.  NaN (a zero-
+// variance column gives 0/0) orders last, as torch.sort does in transformers' _median_filter:
+// fminf / fmaxf would drop it, so a NaN enters the network as +inf and the result is NaN when
+// the median's slot lies among the NaNs.
 template <int WC>
 __device__ __forceinline__ float align_median(const float* __restrict__ scores, const float* __restrict__ stats,
                                               const float* __restrict__ cs, int64_t row, int f, int F, int W,
@@ -223,6 +226,7 @@ __device__ __forceinline__ float align_median(const float* __restrict__ scores, 
     constexpr int CAP = WC ? WC : ALIGN_MAX_WIDTH;
     const int w = WC ? WC : W, pad = w / 2;
     float v[CAP];
+    int n_nan = 0;
 #pragma unroll
     for (int k = 0; k < CAP; ++k) {
         if (k >= w) {
@@ -232,7 +236,9 @@ __device__ __forceinline__ float align_median(const float* __restrict__ scores, 
         int g = f + k - pad;
         g = g < 0 ? -g : g;
         g = g >= F ? 2 * (F - 1) - g : g;
-        v[k] = (align_prob(scores, stats, row, g, TK) - cs[2 * g]) / cs[2 * g + 1];
+        const float z = (align_prob(scores, stats, row, g, TK) - cs[2 * g]) / cs[2 * g + 1];
+        n_nan += z != z;
+        v[k] = z != z ? INFINITY : z;
     }
     // full compare-exchange network (every pair, fixed loops: the array stays in registers)
 #pragma unroll
@@ -247,7 +253,7 @@ __device__ __forceinline__ float align_median(const float* __restrict__ scores, 
 #pragma unroll
     for (int k = 0; k < CAP; ++k)
         if (k == pad) r = v[k];
-    return r;
+    return pad >= w - n_nan ? NAN : r;
 }
 
 // grid (frame blocks, T rows, slots): M[t][f] = mean over heads (list order) of the median-

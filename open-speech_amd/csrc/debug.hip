@@ -1126,6 +1126,205 @@ int osw_debug_mel_windows(osw_ctx* c, const osw_window* windows, int32_t n, void
     });
 }
 
+// ---- the word-timestamp alignment kernels, one production launcher per call (osw.h) ----
+namespace {
+extern "C++" {
+template <typename T>
+T* upload(osw_ctx* c, const T* src, size_t n, TmpBufs& tmp) {
+    T* d = dalloc<T>(n, tmp.v);
+    HIPCHK(hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    return d;
+}
+}
+
+// rows' slots: -1 (not aligned) or distinct indices below n_slots (two rows of one slot would race)
+void require_slots(const int32_t* slot, int rows, int n_slots) {
+    std::vector<char> seen((size_t)n_slots, 0);
+    for (int r = 0; r < rows; ++r) {
+        REQUIRE(slot[r] >= -1 && slot[r] < n_slots, "slot outside [-1, n_slots)");
+        if (slot[r] < 0) continue;
+        REQUIRE(!seen[slot[r]], "a slot appears twice");
+        seen[slot[r]] = 1;
+    }
+}
+}  // namespace
+
+int osw_debug_align_post(osw_ctx* c, const float* scores, int32_t n_slots, int32_t n_heads, int32_t pstride, int32_t TK,
+                         const int32_t* len, const int32_t* head, const int32_t* frames, const int32_t* width,
+                         float* stats, float* colstats, float* M) {
+    return guard([&] {
+        REQUIRE(c && scores && len && head && frames && width && stats && colstats && M, "null argument");
+        REQUIRE(n_slots >= 1 && n_slots <= 64 && n_heads >= 1 && n_heads <= 64, "slots / heads out of range");
+        REQUIRE(pstride >= 16 && pstride % 16 == 0 && pstride <= 448, "pstride: a multiple of 16, at most 448");
+        REQUIRE(TK >= 1 && TK <= 4096, "TK out of range");
+        for (int s = 0; s < n_slots; ++s) {
+            REQUIRE(head[s] == 1 || head[s] == 3, "head: 1 or 3");
+            REQUIRE(len[s] <= pstride && len[s] >= head[s] + 2, "len outside [head + 2, pstride]");
+            REQUIRE(frames[s] >= 1 && frames[s] <= TK, "frames outside [1, TK]");
+            REQUIRE(width[s] >= 1 && width[s] % 2 == 1 && width[s] <= ALIGN_MAX_WIDTH, "width: odd, at most 15");
+        }
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const size_t rows = (size_t)n_slots * n_heads * pstride;
+        const size_t ns = rows * TK, nst = rows * 2, ncs = (size_t)n_slots * n_heads * TK * 2;
+        const size_t nm = (size_t)n_slots * pstride * TK;
+        float* ds = upload(c, scores, ns, tmp);
+        std::vector<int> meta((size_t)4 * n_slots);  // len, head, frames, width
+        for (int s = 0; s < n_slots; ++s) {
+            meta[s] = len[s];
+            meta[n_slots + s] = head[s];
+            meta[2 * n_slots + s] = frames[s];
+            meta[3 * n_slots + s] = width[s];
+        }
+        int* dm = upload(c, meta.data(), meta.size(), tmp);
+        float* dst = result_buf(c, (int64_t)nst, tmp);
+        float* dcs = result_buf(c, (int64_t)ncs, tmp);
+        float* dM = result_buf(c, (int64_t)nm, tmp);
+        launch_align_post(ds, n_slots, n_heads, pstride, TK, dm, dm + n_slots, dm + 2 * n_slots, dm + 3 * n_slots, dst,
+                          dcs, dM, c->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(stats, dst, nst * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(colstats, dcs, ncs * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(M, dM, nm * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
+int osw_debug_align_tail(osw_ctx* c, const float* logits, int32_t rows, int32_t V, int32_t eot, int32_t ctx, int32_t pos,
+                         const int32_t* slot, const int32_t* len, const int32_t* head, const int32_t* forced,
+                         int32_t n_slots, float* token_logprob, int32_t* cur_tok, int32_t* done) {
+    return guard([&] {
+        REQUIRE(c && logits && slot && len && head && forced && token_logprob && cur_tok && done, "null argument");
+        REQUIRE(rows >= 1 && rows <= 1024 && n_slots >= 1 && n_slots <= 1024, "rows / slots out of range");
+        REQUIRE(V >= 1 && V <= 65536 && eot >= 1 && eot <= V, "eot outside [1, V]");
+        REQUIRE(ctx >= 1 && ctx <= 448 && pos >= 0, "ctx / pos out of range");
+        require_slots(slot, rows, n_slots);
+        for (int r = 0; r < rows; ++r) {
+            REQUIRE(head[r] == 1 || head[r] == 3, "head: 1 or 3");
+            REQUIRE(len[r] >= 0 && len[r] <= ctx, "len outside [0, ctx]");
+            for (int i = 0; i < len[r]; ++i)
+                REQUIRE(forced[(size_t)r * ctx + i] >= 0 && forced[(size_t)r * ctx + i] < V,
+                        "forced token outside the vocabulary");
+        }
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        std::vector<SelState> st((size_t)rows);
+        for (int r = 0; r < rows; ++r) {
+            st[r] = SelState{};
+            st[r].done = done[r];
+        }
+        float* dl = upload(c, logits, (size_t)rows * V, tmp);
+        std::vector<int> meta((size_t)1 + 3 * rows);  // pos, slot, len, head
+        meta[0] = pos;
+        for (int r = 0; r < rows; ++r) {
+            meta[1 + r] = slot[r];
+            meta[1 + rows + r] = len[r];
+            meta[1 + 2 * rows + r] = head[r];
+        }
+        int* dm = upload(c, meta.data(), meta.size(), tmp);
+        int* df = upload(c, forced, (size_t)rows * ctx, tmp);
+        float* dlp = upload(c, token_logprob, (size_t)n_slots * ctx, tmp);
+        int* dct = upload(c, cur_tok, (size_t)rows, tmp);
+        SelState* dst = upload(c, st.data(), (size_t)rows, tmp);
+        launch_align_tail(dl, rows, V, eot, ctx, dm, dm + 1, dm + 1 + rows, dm + 1 + 2 * rows, df, dlp, dct, dst,
+                          c->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(token_logprob, dlp, (size_t)n_slots * ctx * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(cur_tok, dct, (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(st.data(), dst, (size_t)rows * sizeof(SelState), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (int r = 0; r < rows; ++r) done[r] = st[r].done;
+    });
+}
+
+int osw_debug_align_self_attn(osw_ctx* c, const float* qkv_slabs, int32_t ks, const float* bias, float* kcache,
+                              float* vcache, int32_t rows, int32_t H, int32_t ctx, int32_t pos, const int32_t* done,
+                              float* out) {
+    return guard([&] {
+        REQUIRE(c && qkv_slabs && bias && kcache && vcache && done && out, "null argument");
+        REQUIRE(ks >= 1 && ks <= 32, "ks out of range");
+        REQUIRE(rows >= 1 && rows <= 1024 && H >= 1 && H <= 20, "rows / heads out of range");
+        REQUIRE(ctx >= 1 && ctx <= 448, "ctx out of range (the kernel's score buffer holds 512)");
+        REQUIRE(pos >= 0, "negative position");  // (one past ctx - 1 is clamped by the kernel)
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const int D = H * 64;
+        const size_t nq = (size_t)ks * rows * 3 * D, nkv = (size_t)rows * H * ctx * 64, no = (size_t)rows * D;
+        std::vector<SelState> st((size_t)rows);
+        for (int r = 0; r < rows; ++r) {
+            st[r] = SelState{};
+            st[r].done = done[r];
+        }
+        float* dq = upload(c, qkv_slabs, nq, tmp);
+        float* db = upload(c, bias, (size_t)3 * D, tmp);
+        float* dk = upload(c, kcache, nkv, tmp);
+        float* dv = upload(c, vcache, nkv, tmp);
+        int* dpos = upload(c, &pos, 1, tmp);
+        SelState* dst = upload(c, st.data(), (size_t)rows, tmp);
+        h16* dout = dalloc<h16>(2 * no, tmp.v);  // hi, then lo
+        HIPCHK(hipMemsetAsync(dout, 0xff, 2 * no * 2, c->stream));
+        launch_align_self_attn(dq, ks, db, dk, dv, dpos, rows, H, ctx, dout, (int64_t)no, dst, c->stream);
+        HIPCHK(hipGetLastError());
+        std::vector<h16> back(2 * no);
+        HIPCHK(hipMemcpyAsync(back.data(), dout, 2 * no * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(kcache, dk, nkv * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(vcache, dv, nkv * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < no; ++i) out[i] = (float)back[i] + (float)back[no + i];
+    });
+}
+
+int osw_debug_align_scores(osw_ctx* c, const float* q_slabs, int32_t ks, const float* bias, const void* K, int32_t rows,
+                           int32_t H, int32_t T, const int32_t* layer_heads, int32_t n_layer_heads, int32_t n_heads,
+                           int32_t pos, const int32_t* slot, const int32_t* len, int32_t pstride, int32_t n_slots,
+                           float* scores) {
+    return guard([&] {
+        REQUIRE(c && q_slabs && K && layer_heads && slot && len && scores, "null argument");
+        REQUIRE(ks >= 1 && ks <= 32, "ks out of range");
+        REQUIRE(rows >= 1 && rows <= 1024 && H >= 1 && H <= 20 && T >= 1 && T <= 4096, "rows / heads / T out of range");
+        REQUIRE(n_heads >= 1 && n_heads <= 64 && n_layer_heads >= 1 && n_layer_heads <= n_heads, "head list out of range");
+        REQUIRE(n_slots >= 1 && n_slots <= 1024 && pstride >= 1 && pstride <= 448 && pos >= 0, "slots / pstride / pos out of range");
+        std::vector<char> seen((size_t)n_heads, 0);
+        for (int e = 0; e < n_layer_heads; ++e) {
+            const int h = layer_heads[2 * e], hi = layer_heads[2 * e + 1];
+            REQUIRE(h >= 0 && h < H && hi >= 0 && hi < n_heads && !seen[hi], "layer_heads: {head < H, distinct head_idx < n_heads}");
+            seen[hi] = 1;
+        }
+        require_slots(slot, rows, n_slots);
+        for (int r = 0; r < rows; ++r) REQUIRE(len[r] >= 0 && len[r] <= pstride, "len outside [0, pstride]");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        GateLock gate_(capture_gate());
+        TmpBufs tmp;
+        const int D = H * 64;
+        const size_t nq = (size_t)ks * rows * D, nk = (size_t)rows * H * T * 64;
+        const size_t ns = (size_t)n_slots * n_heads * pstride * T;
+        float* dq = upload(c, q_slabs, nq, tmp);
+        float* db = bias ? upload(c, bias, (size_t)D, tmp) : nullptr;
+        h16* dk = upload(c, (const h16*)K, nk, tmp);
+        std::vector<int> meta((size_t)1 + 2 * rows + 2 * n_layer_heads);  // pos, slot, len, layer_heads
+        meta[0] = pos;
+        for (int r = 0; r < rows; ++r) {
+            meta[1 + r] = slot[r];
+            meta[1 + rows + r] = len[r];
+        }
+        for (int i = 0; i < 2 * n_layer_heads; ++i) meta[1 + 2 * rows + i] = layer_heads[i];
+        int* dm = upload(c, meta.data(), meta.size(), tmp);
+        float* dsc = upload(c, scores, ns, tmp);
+        launch_align_scores(dq, ks, db, dk, rows, H, T, dm + 1 + 2 * rows, n_layer_heads, n_heads, dm, dm + 1,
+                            dm + 1 + rows, dsc, pstride, c->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(scores, dsc, ns * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
 int osw_debug_hold_capture(osw_ctx* c, int32_t hold_ms) {
     return guard([&] {
         REQUIRE(c, "null ctx");

@@ -534,6 +534,92 @@ class WhisperEngine:
                                           _i32p(fi), C.byref(n)), "osw_debug_dtw")
         return ti[:n.value].copy(), fi[:n.value].copy()
 
+    def debug_align_post(self, scores: np.ndarray, length, head, frames, width):
+        """launch_align_post alone (osw_debug_align_post): scores fp32 [slots][heads][pstride][TK], one
+        len / head / frames / width per slot.  Returns (stats [slots][heads][pstride][2], colstats
+        [slots][heads][TK][2], M [slots][pstride][TK]); what the kernels did not write holds 0xff bytes."""
+        s = np.ascontiguousarray(scores, dtype=np.float32)
+        n_slots, n_heads, pstride, TK = s.shape
+        meta = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (length, head, frames, width)]
+        if any(a.shape != (n_slots,) for a in meta):
+            raise ValueError("one len, head, frames and width per slot")
+        stats = np.empty((n_slots, n_heads, pstride, 2), np.float32)
+        cs = np.empty((n_slots, n_heads, TK, 2), np.float32)
+        M = np.empty((n_slots, pstride, TK), np.float32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(self.lib.osw_debug_align_post(self.ctx, s.ctypes.data_as(fp), n_slots, n_heads, pstride, TK,
+                                                 *[_i32p(a) for a in meta], stats.ctypes.data_as(fp),
+                                                 cs.ctypes.data_as(fp), M.ctypes.data_as(fp)), "osw_debug_align_post")
+        return stats, cs, M
+
+    def debug_align_tail(self, logits: np.ndarray, eot: int, pos: int, slot, length, head, forced: np.ndarray,
+                         token_logprob: np.ndarray, cur_tok, done):
+        """launch_align_tail alone (osw_debug_align_tail): logits fp32 [rows][V], forced [rows][ctx],
+        token_logprob [slots][ctx].  Returns copies (token_logprob, cur_tok, done) as the launch left them."""
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        rows, V = lg.shape
+        f = np.ascontiguousarray(forced, dtype=np.int32)
+        lp = np.array(token_logprob, dtype=np.float32, order="C", ndmin=2)
+        ctx = f.shape[1]
+        per_row = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (slot, length, head)]
+        ct = np.array(cur_tok, dtype=np.int32, order="C").reshape(-1)
+        dn = np.array(done, dtype=np.int32, order="C").reshape(-1)
+        if f.shape != (rows, ctx) or lp.shape[1] != ctx or any(a.shape != (rows,) for a in per_row + [ct, dn]):
+            raise ValueError("shapes: logits [rows][V], forced [rows][ctx], token_logprob [slots][ctx], the rest [rows]")
+        fp = C.POINTER(C.c_float)
+        _lib.check(self.lib.osw_debug_align_tail(self.ctx, lg.ctypes.data_as(fp), rows, V, int(eot), ctx, int(pos),
+                                                 *[_i32p(a) for a in per_row], _i32p(f), lp.shape[0],
+                                                 lp.ctypes.data_as(fp), _i32p(ct), _i32p(dn)), "osw_debug_align_tail")
+        return lp, ct, dn
+
+    def debug_align_self_attn(self, qkv_slabs: np.ndarray, bias: np.ndarray, kcache: np.ndarray, vcache: np.ndarray,
+                              pos: int, done):
+        """launch_align_self_attn alone (osw_debug_align_self_attn): qkv_slabs fp32 [ks][rows][3D], bias
+        [3D], fp32 caches [rows][H][ctx][64], done [rows].  Returns (out fp32 [rows][D] = hi + lo, NaN
+        where nothing was written, kcache, vcache), the caches as the kernel left them (copies)."""
+        q = np.ascontiguousarray(qkv_slabs, dtype=np.float32)
+        ks, rows, D3 = q.shape
+        kc = np.array(kcache, dtype=np.float32, order="C")
+        vc = np.array(vcache, dtype=np.float32, order="C")
+        b = np.ascontiguousarray(bias, dtype=np.float32)
+        dn = np.ascontiguousarray(done, dtype=np.int32).reshape(-1)
+        H, ctx = kc.shape[1:3]
+        if D3 != 3 * 64 * H or kc.shape != (rows, H, ctx, 64) or vc.shape != kc.shape or b.shape != (D3,) or \
+                dn.shape != (rows,):
+            raise ValueError("shapes: qkv [ks][rows][3D], bias [3D], caches [rows][H][ctx][64], done [rows]")
+        out = np.empty((rows, 64 * H), np.float32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(self.lib.osw_debug_align_self_attn(self.ctx, q.ctypes.data_as(fp), ks, b.ctypes.data_as(fp),
+                                                      kc.ctypes.data_as(fp), vc.ctypes.data_as(fp), rows, H, ctx,
+                                                      int(pos), _i32p(dn), out.ctypes.data_as(fp)),
+                   "osw_debug_align_self_attn")
+        return out, kc, vc
+
+    def debug_align_scores(self, q_slabs: np.ndarray, bias, K: np.ndarray, layer_heads, n_heads: int, pos: int,
+                           slot, length, scores: np.ndarray) -> np.ndarray:
+        """launch_align_scores alone (osw_debug_align_scores): q_slabs fp32 [ks][rows][D], bias [D] or
+        None, K fp16 [rows][H][T][64], layer_heads pairs (head, head_idx), scores fp32
+        [slots][n_heads][pstride][T].  Returns a copy of scores as the launch left it."""
+        q = np.ascontiguousarray(q_slabs, dtype=np.float32)
+        K = np.ascontiguousarray(K, dtype=np.float16)
+        ks, rows, Dm = q.shape
+        H, T = K.shape[1:3]
+        lh = np.ascontiguousarray(layer_heads, dtype=np.int32).reshape(-1, 2)
+        sc = np.array(scores, dtype=np.float32, order="C")
+        sl = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+        ln = np.ascontiguousarray(length, dtype=np.int32).reshape(-1)
+        b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+        if K.shape != (rows, H, T, 64) or Dm != 64 * H or sc.ndim != 4 or sc.shape[1] != n_heads or sc.shape[3] != T or \
+                sl.shape != (rows,) or ln.shape != (rows,) or (b is not None and b.shape != (Dm,)):
+            raise ValueError("shapes: q [ks][rows][D], K [rows][H][T][64], scores [slots][n_heads][pstride][T]")
+        fp = C.POINTER(C.c_float)
+        _lib.check(self.lib.osw_debug_align_scores(self.ctx, q.ctypes.data_as(fp), ks,
+                                                   None if b is None else b.ctypes.data_as(fp),
+                                                   K.ctypes.data_as(C.c_void_p), rows, H, T, _i32p(lh), len(lh),
+                                                   int(n_heads), int(pos), _i32p(sl), _i32p(ln), sc.shape[2],
+                                                   sc.shape[0], sc.ctypes.data_as(fp)), "osw_debug_align_scores")
+        return sc
+
     def debug_history_rules(self, logits: np.ndarray, tokens: np.ndarray, n_hist, repetition_penalty: float = 1.0,
                             no_repeat_ngram_size: int = 0) -> np.ndarray:
         """The history-rules kernel alone: logits [rows][V] with row r's history

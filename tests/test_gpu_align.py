@@ -65,12 +65,14 @@ DTW_SHAPES = [(1, 1), (2, 1), (1, 7), (5, 3), (38, 1500), (257, 300), (445, 1500
 
 
 @pytest.mark.parametrize("shape", DTW_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
-@pytest.mark.parametrize("kind", ["ties", "random"])
+@pytest.mark.parametrize("kind", ["ties", "random", "nan"])
 def test_dtw_kernel_equals_numpy(tiny, shape, kind):
     d, eng, _, _ = tiny
     T, F = shape
     rng = np.random.default_rng(100 * T + F)
     x = align_ref.tie_matrix(rng, T, F) if kind == "ties" else rng.standard_normal((T, F)).astype(np.float32)
+    if kind == "nan":   # a few NaN cells: the kernel and align_ref.dtw apply the same comparisons
+        x[rng.integers(0, T, 6), rng.integers(0, F, 6)] = np.nan
     ti, fi = eng.debug_dtw(x)
     rt, rf = align_ref.dtw(x)
     assert len(ti) == len(rt)
