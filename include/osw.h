@@ -375,7 +375,55 @@ int osw_session_step(osw_ctx* ctx, int32_t max_chunks, int32_t refill_min, osw_w
 /* Frees the resident log-mel of clip `clip` (no queued window may still read it; windows
  * already admitted were staged and are unaffected). */
 int osw_session_release_clip(osw_ctx* ctx, int64_t clip);
+/* Ends the session: queued and decoding windows are dropped, held windows (below) and resident
+ * clips freed. */
 int osw_session_end(osw_ctx* ctx);
+
+/* ---- word timestamps on a session: hold, align, release ----
+ * The alignment pass (osw_align_windows, below) needs a window's cross-K/V after the caller has
+ * split the window into segments and knows its text tokens, but a session gives a finished
+ * window's slot to the next admission in the call that returns it.  With hold on, the slot
+ * waits: a window osw_session_step returns is HELD, its cross-K/V stays as the encoder left it,
+ * nothing is admitted into its slot, osw_session_step never reports it again and it no longer
+ * counts in *n_active (windows decoding).  The caller then aligns it (osw_session_align) or lets
+ * it go (osw_session_release); either frees the slot for the next admission.  A caller is
+ * expected to do so for everything a step returned before its next step: when nothing decodes,
+ * every slot is held and windows are queued, osw_session_step returns at once with *n_done == 0,
+ * launches nothing and waits for nothing.  osw_session_end frees whatever is still held.
+ * A slot is free, decoding or held; the transitions are those of csrc/slots.h.
+ *
+ * osw_session_hold: valid after osw_session_begin and before the session's first
+ * osw_session_add, else OSW_ESTATE (also without an open session).  enable != 0 turns hold on
+ * for this session; a session that never calls it behaves as above ("leaves its slot at once"),
+ * bit for bit.  In a hold-mode session a window is named by its tag from the step that returns
+ * it to its align or release, so osw_session_add refuses (OSW_EINVAL, nothing queued) a tag that a
+ * queued, decoding or held window of the session already carries, or that appears twice in the
+ * call; a tag is free again once its window was aligned or released.
+ *
+ * osw_session_align: the alignment of n held windows, then their slots freed.  tags[i] names
+ * entry i's window; w[i] is an osw_align_window (below) whose `window` is ignored and whose other
+ * fields, and `res`, mean what they mean for osw_align_windows, with the same OSW_EINVAL checks
+ * (n_tokens == 0 included: an empty result, the slot freed).  Every tag must be held and the tags
+ * distinct: a tag that is unknown, still queued or decoding, or already aligned or released is
+ * OSW_EINVAL.  A refused call (any OSW_EINVAL above) changes nothing: no slot is freed, nothing
+ * is launched.  The pass runs one decoder row per entry on row state of its own and reads each
+ * row's cross-K/V from its window's slot; it writes nothing a decoding row reads, so every other
+ * window of the session still decodes exactly as it does alone, and entry i's result is bit for
+ * bit what osw_align_windows returns for that window after a batched decode.  After the call
+ * osw_get_alignment_matrix(ctx, i, ...) returns M of entry i.  Replaces the same ctranslate2
+ * Whisper.align call as osw_align_windows [upstream], for windows decoded in a session.
+ *
+ * osw_session_release: frees the slots of n held windows without aligning them (a window skipped
+ * as silence, one without text tokens, a failed request).  Tags as for osw_session_align: all
+ * held and distinct, else OSW_EINVAL and nothing is freed.  n == 0 is a no-op.
+ *
+ * osw_align_windows stays OSW_EINVAL while a session is open, with or without hold. */
+struct osw_align_window;
+struct osw_align_result;
+int osw_session_hold(osw_ctx* ctx, int32_t enable);
+int osw_session_align(osw_ctx* ctx, int32_t n, const int64_t* tags, const struct osw_align_window* w,
+                      struct osw_align_result* res);
+int osw_session_release(osw_ctx* ctx, int32_t n, const int64_t* tags);
 
 /* ---- confidences: per-token log-probabilities and language probabilities ----
  * Off by default.  On, every decode entry point (osw_decode_windows, osw_transcribe_batch,

@@ -129,6 +129,10 @@ _SIGS = {
                                    P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
     "osw_session_release_clip": (C.c_int, [C.c_void_p, C.c_int64]),
     "osw_session_end": (C.c_int, [C.c_void_p]),
+    # word timestamps on a session: finished windows keep their slots until aligned or released
+    "osw_session_hold": (C.c_int, [C.c_void_p, C.c_int32]),
+    "osw_session_align": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_int64), P(osw_align_window), P(osw_align_result)]),
+    "osw_session_release": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_int64)]),
     # confidences (replace ctranslate2's return_scores per token, faster-whisper's language_probability /
     # all_language_probs and WhisperModel.detect_language)
     "osw_set_confidences": (C.c_int, [C.c_void_p, C.c_int32]),

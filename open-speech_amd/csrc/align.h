@@ -26,7 +26,7 @@ struct AlignCapture {
 
 void launch_align_scores(const float* part, int ks, const float* bias, const h16* xk, int rows, int H, int T,
                          const int* layer_heads, int n_layer_heads, int n_heads, const int* pos, const int* slot,
-                         const int* len, float* scores, int pstride, hipStream_t s);
+                         const int* len, float* scores, int pstride, hipStream_t s, const int* wmap = nullptr);
 // the forced pass's self-attention in fp32 (kc / vc: this layer's fp32 cache, [rows][H][ctx][64])
 void launch_align_self_attn(const float* part, int ks, const float* bias, float* kc, float* vc, const int* pos, int B,
                             int H, int ctx, h16* out, int64_t lo_off, const SelState* st, hipStream_t s);

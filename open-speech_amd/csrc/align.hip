@@ -34,14 +34,16 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 
 // grid (layer heads x rows, key blocks of 256): q of (row, head) exactly as the
 // cross-attention kernels form it (reduce_head: slabs + bias, rounded to fp16), dotted with
-// the window's resident keys in fp32, times the exact 1/8
+// the window's resident keys in fp32, times the exact 1/8.  wmap (osw_session_align): row b
+// reads the keys of window wmap[b], one uniform load per workgroup; null = the identity.  Only
+// the key address depends on it: the q slabs, the slot and the scores row keep b.
 __global__ __launch_bounds__(256) void align_scores_kernel(const float* __restrict__ part, int ks,
                                                            const float* __restrict__ bias,
                                                            const h16* __restrict__ xk, int rows, int H, int T,
                                                            const int* __restrict__ lh, int n_lh, int n_heads,
                                                            const int* __restrict__ pos, const int* __restrict__ slot,
                                                            const int* __restrict__ len, float* __restrict__ scores,
-                                                           int pstride) {
+                                                           int pstride, const int* __restrict__ wmap) {
     __shared__ h16 q16[HD];
     __shared__ float red4[256];
     __shared__ float qf[HD];
@@ -55,7 +57,7 @@ __global__ __launch_bounds__(256) void align_scores_kernel(const float* __restri
     __syncthreads();
     const int key = blockIdx.y * 256 + threadIdx.x;
     if (key >= T) return;
-    const h16* kr = xk + (((int64_t)b * H + h) * T + key) * HD;
+    const h16* kr = xk + (((int64_t)(wmap ? wmap[b] : b) * H + h) * T + key) * HD;
     float acc = 0.f;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -366,10 +368,10 @@ __global__ __launch_bounds__(256) void align_dtw_kernel(const float* __restrict_
 
 void launch_align_scores(const float* part, int ks, const float* bias, const h16* xk, int rows, int H, int T,
                          const int* layer_heads, int n_layer_heads, int n_heads, const int* pos, const int* slot,
-                         const int* len, float* scores, int pstride, hipStream_t s) {
+                         const int* len, float* scores, int pstride, hipStream_t s, const int* wmap) {
     if (n_layer_heads <= 0) return;
     align_scores_kernel<<<dim3(n_layer_heads * rows, (T + 255) / 256), 256, 0, s>>>(
-        part, ks, bias, xk, rows, H, T, layer_heads, n_layer_heads, n_heads, pos, slot, len, scores, pstride);
+        part, ks, bias, xk, rows, H, T, layer_heads, n_layer_heads, n_heads, pos, slot, len, scores, pstride, wmap);
 }
 
 void launch_align_self_attn(const float* part, int ks, const float* bias, float* kc, float* vc, const int* pos, int B,

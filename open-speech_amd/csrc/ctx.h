@@ -206,13 +206,17 @@ struct AlignBufs {
     float *tokprob = nullptr /* log-probabilities */, *scores = nullptr, *stats = nullptr, *colstats = nullptr, *M = nullptr;
     unsigned char* trace = nullptr;
     float *kc32 = nullptr, *vc32 = nullptr;  // fp32 self-K/V cache of the forced pass, [L][cap_rows][H][ctx][64]
+    // osw_session_align: the pass's own row state ([R] each; one scalar position), so that the
+    // session's decoding rows keep theirs (c->sel / c->cur_tok / c->pos)
+    SelState* sel = nullptr;
+    int *cur_tok = nullptr, *pos = nullptr;
     int cap_slots = 0, cap_pstride = 0, cap_heads = 0, cap_rows = 0;
     int64_t gen = 0;                // bumps when a buffer moves or the heads change (decode-graph key)
     std::vector<int> heads;         // the caller's (layer, head) pairs; empty: the default set
     std::vector<int> layer_first;   // [L + 1] offsets into lh (pairs), heads grouped by layer
     int n_heads = 0;
     bool heads_dirty = true;
-    std::vector<int> win, T, F;     // last call: window index, rows and frames of each slot
+    std::vector<int> win, T, F;     // last call: window index (osw_session_align: entry index), rows and frames of each slot
     int pstride = 0;
 };
 }  // namespace osw
@@ -327,7 +331,7 @@ struct osw_ctx {
     bool conf_valid = false;
 
     AlignBufs al;
-    const AlignCapture* acap = nullptr;  // set while osw_align_windows steps the decoder
+    const AlignCapture* acap = nullptr;  // set while osw_align_windows / osw_session_align steps the decoder
 
     // profiling
     bool prof = false;
@@ -398,6 +402,8 @@ void encoder_layer(osw_ctx* c, int i, int nb);
 std::vector<int> pack_windows(osw_ctx* c, const osw_window* wins, int n);
 void encode(osw_ctx* c, const osw_window* wins, int n, const int* slots = nullptr);
 void reserve_clips(osw_ctx* c, int n);
+// osw_session_align's pass: entry i of w aligned over the cross-K/V of session slot slots[i]
+void align_held(osw_ctx* c, int n, const int* slots, const osw_align_window* w, osw_align_result* r);
 
 // decode_host.hip
 bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf = nullptr);

@@ -4,14 +4,15 @@
 
 namespace osw {
 // Alignment pass only (c->acap set by align()): the raw scaled scores of layer l's alignment
-// heads, from the same q slabs the cross-attention launch beside it reduces
+// heads, from the same q slabs the cross-attention launch beside it reduces, and through the
+// same window map (c->xmap: osw_session_align's rows read their held slots' keys)
 void align_capture(osw_ctx* c, int l, const float* part, int ks, int nb, int64_t xkv_which) {
     const AlignCapture& a = *c->acap;
     const int first = a.layer_first[l], cnt = a.layer_first[l + 1] - first;
     if (cnt <= 0) return;
     launch_align_scores(part, ks, WF(c, "dec.l" + std::to_string(l) + ".xq.b"), c->XKV + (2 * l) * xkv_which, nb,
                         c->d.n_text_head, c->T, a.layer_heads + 2 * first, cnt, a.n_heads, c->pos, a.slot, a.len,
-                        a.scores, a.pstride, c->stream);
+                        a.scores, a.pstride, c->stream, c->xmap);
 }
 
 // ---------------------------- decoder --------------------------------------

@@ -605,6 +605,9 @@ void align_reserve(osw_ctx* c, int n_slots, int pstride, int rows) {
         A.path_len = dalloc<int>(c->B, o);
         A.tf = dalloc<int>((size_t)c->B * ctx, o);
         A.tokprob = dalloc<float>((size_t)c->B * ctx, o);
+        A.sel = dalloc<SelState>(c->R, o);
+        A.cur_tok = dalloc<int>(c->R, o);
+        A.pos = dalloc<int>(c->R, o);
     }
     if (n_slots <= A.cap_slots && pstride <= A.cap_pstride && A.n_heads <= A.cap_heads) return;
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -625,25 +628,31 @@ void align_reserve(osw_ctx* c, int n_slots, int pstride, int rows) {
     ++A.gen;
 }
 
-// Teacher-forced pass over the resident cross-K/V of the last encode call, one decoder row
-// per encoded window (rows not aligned are marked finished, which every attention kernel
-// skips), through decoder_step with the capture armed; then M, DTW and the read-back.
-void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
+// The argument checks and the forced sequences of one alignment call, packed per decoder row.
+// Host only: nothing is launched and nothing of the context changes, so a refused call leaves
+// no trace.  Entry i goes to decoder row w[i].window (osw_align_windows: one row per encoded
+// window) or, with `compact`, to row i (osw_session_align, which ignores w[i].window).
+struct AlignPack {
+    std::vector<int> slot, len, forced, head;        // per decoder row
+    std::vector<int> s_len, s_fr, s_w, s_T, s_head;  // per aligned window (slot)
+    std::vector<int> win, T, F;                      // AlignBufs::win / T / F of this call
+    std::vector<int> row;                            // entry i's decoder row
+    int pmax = 0, eot = 0;
+};
+AlignPack align_pack(osw_ctx* c, int n, const osw_align_window* w, const osw_align_result* r, int nb, bool compact) {
     REQUIRE(n >= 1 && w && r && r->token_frame && r->token_prob, "null align argument");
     const osw_dims& d = c->d;
-    const int ctx = d.n_text_ctx, V = d.n_vocab, nb = c->n_encoded;
-    REQUIRE(nb >= 1 && nb <= c->R, "no encoded windows are resident (encode or decode first)");
-    REQUIRE(n <= nb, "more windows than the last encode call holds");
-    AlignBufs& A = c->al;
-    std::vector<int> slot(nb, -1), len(nb, 0), forced((size_t)nb * ctx, 0);
-    std::vector<int> s_len, s_fr, s_w, s_T, s_head, head(nb, 3);
-    A.win.clear();
-    A.T.clear();
-    A.F.clear();
-    int pmax = 0;
-    const int eot = w[0].eot;
+    const int ctx = d.n_text_ctx, V = d.n_vocab;
+    AlignPack P;
+    std::vector<int>&slot = P.slot, &len = P.len, &forced = P.forced, &head = P.head;
+    slot.assign(nb, -1), len.assign(nb, 0), forced.assign((size_t)nb * ctx, 0), head.assign(nb, 3);
+    std::vector<int>&s_len = P.s_len, &s_fr = P.s_fr, &s_w = P.s_w, &s_T = P.s_T, &s_head = P.s_head;
+    int& pmax = P.pmax;
+    const int eot = P.eot = w[0].eot;
     for (int i = 0; i < n; ++i) {
-        const osw_align_window& a = w[i];
+        osw_align_window a = w[i];
+        if (compact) a.window = i;
+        P.row.push_back(a.window);
         REQUIRE(a.window >= 0 && a.window < nb, "align: stale window index");
         REQUIRE(slot[a.window] < 0 && len[a.window] == 0, "align: a window appears twice");
         REQUIRE(a.n_tokens >= 0 && (a.n_tokens == 0 || a.tokens), "align: bad token list");
@@ -672,27 +681,57 @@ void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
             f[hd + 1 + k] = a.tokens[k];
         }
         f[hd + 1 + a.n_tokens] = eot;
-        const int P = a.n_tokens + hd + 2;
+        const int plen = a.n_tokens + hd + 2;
         head[a.window] = hd;
         s_head.push_back(hd);
-        slot[a.window] = (int)A.win.size();
-        len[a.window] = P;
-        A.win.push_back(a.window);
-        A.T.push_back(a.n_tokens + 1);
-        A.F.push_back(F);
-        s_len.push_back(P);
+        slot[a.window] = (int)P.win.size();
+        len[a.window] = plen;
+        P.win.push_back(a.window);
+        P.T.push_back(a.n_tokens + 1);
+        P.F.push_back(F);
+        s_len.push_back(plen);
         s_fr.push_back(F);
         s_w.push_back(W);
         s_T.push_back(a.n_tokens + 1);
-        pmax = std::max(pmax, P);
+        pmax = std::max(pmax, plen);
     }
     for (int b = 0; b < nb; ++b) len[b] = std::max(len[b], 0);
+    return P;
+}
+
+// What the forced pass may write of the decoder's row state, and how its rows find their
+// cross-K/V.  osw_align_windows: the context's own state (nothing else is decoding), row b
+// attends encoded window b (wmap null, plane 0: the step's own row count).  osw_session_align:
+// the pass's own SelState / token / position buffers (AlignBufs), since the context's belong to
+// the rows that are still decoding, and row i attends the held slot wmap[i] of `plane` windows.
+struct AlignRows {
+    bool own;         // AlignBufs::sel / cur_tok / pos instead of the context's
+    const int* wmap;  // host, nb entries, or null (the identity)
+    int plane;        // cross-K/V windows per plane (c->xkv_windows during the pass)
+};
+
+// The core both entry points share: a teacher-forced pass of nb decoder rows through decoder_step
+// with the capture armed (rows not aligned are marked finished, which every attention kernel
+// skips), then M, DTW and the read-back of P's windows into r.
+void align_core(osw_ctx* c, const AlignPack& P, int nb, const AlignRows& rows, int n, const osw_align_window* w,
+                osw_align_result* r) {
+    const osw_dims& d = c->d;
+    const int ctx = d.n_text_ctx, V = d.n_vocab, eot = P.eot, pmax = P.pmax;
+    AlignBufs& A = c->al;
+    const std::vector<int>&slot = P.slot, &len = P.len, &forced = P.forced, &head = P.head;
+    const std::vector<int>&s_len = P.s_len, &s_fr = P.s_fr, &s_w = P.s_w, &s_T = P.s_T, &s_head = P.s_head;
+    A.win = P.win;
+    A.T = P.T;
+    A.F = P.F;
     const int ns = (int)A.win.size();
     if (ns == 0) return;
     align_sync_heads(c);
     const int pstride = (pmax + 15) / 16 * 16;
     align_reserve(c, ns, pstride, nb);
     A.pstride = pstride;
+    SelState* const sel = rows.own ? A.sel : c->sel;
+    int* const cur_tok = rows.own ? A.cur_tok : c->cur_tok;
+    int* const pos = rows.own ? A.pos : c->pos;
     std::vector<SelState> st(nb);
     std::vector<int> first(nb);
     for (int b = 0; b < nb; ++b) {
@@ -712,39 +751,64 @@ void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
     up(A.slot_T, s_T.data(), ns * 4);
     up(A.head, head.data(), nb * 4);
     up(A.slot_head, s_head.data(), ns * 4);
-    up(c->sel, st.data(), nb * sizeof(SelState));
-    up(c->cur_tok, first.data(), nb * 4);
-    HIPCHK(hipMemsetAsync(c->pos, 0, 4, c->stream));
+    up(sel, st.data(), nb * sizeof(SelState));
+    up(cur_tok, first.data(), nb * 4);
+    HIPCHK(hipMemsetAsync(pos, 0, 4, c->stream));
+    if (rows.wmap) up(c->xmap_d, rows.wmap, nb * 4);
     AlignCapture cap;
     cap.scores = A.scores; cap.slot = A.slot; cap.len = A.len; cap.layer_heads = A.lh;
     cap.layer_first = A.layer_first.data(); cap.n_heads = A.n_heads; cap.pstride = pstride;
     cap.kc32 = A.kc32; cap.vc32 = A.vc32;
-    struct Armed {
-        osw_ctx* c;
-        ~Armed() { c->acap = nullptr; }
-    } armed{c};
-    c->acap = &cap;
-    auto one_step = [&] {
-        decoder_step(c, nb, 1, false, nullptr);
-        launch_align_tail(c->logits, nb, V, eot, ctx, c->pos, A.slot, A.len, A.head, A.forced, A.tokprob, c->cur_tok,
-                          c->sel, c->stream);
-        launch_align_bump(c->pos, c->stream);
-    };
-    const int CH = 8;
-    hipGraphExec_t ge = nullptr;
-    if (c->use_graph && !c->prof_eager && pmax >= CH)
-        ge = decode_graph(c, {-77, nb, A.gen, pstride, eot}, one_step, CH);  // its own key: no decode key starts below 1
-    for (int steps = 0; steps < pmax;) {
-        if (ge && pmax - steps >= CH) {
-            HIPCHK(hipGraphLaunch(ge, c->stream));
-            steps += CH;
-        } else {
-            one_step();
-            steps += 1;
+    {
+        // decoder_step reads the row state, the step-counter form, the cache strides and the window
+        // map off the context: the pass puts its own in place and this guard puts back what it
+        // found, on every way out (a decode session goes on with its rows as it left them)
+        struct Armed {
+            osw_ctx* c;
+            SelState* sel = c->sel;
+            int *cur_tok = c->cur_tok, *pos = c->pos;
+            bool row_pos = c->row_pos;
+            int kv_rows = c->kv_rows, xkv_windows = c->xkv_windows;
+            const int* xmap = c->xmap;
+            ~Armed() {
+                c->acap = nullptr;
+                c->sel = sel, c->cur_tok = cur_tok, c->pos = pos;
+                c->row_pos = row_pos, c->kv_rows = kv_rows, c->xkv_windows = xkv_windows;
+                c->xmap = xmap;
+            }
+        } armed{c};
+        c->acap = &cap;
+        c->sel = sel, c->cur_tok = cur_tok, c->pos = pos;
+        c->row_pos = false;  // one scalar position for the pass's rows
+        c->kv_rows = 0;      // kc32 / vc32 hold nb rows per layer
+        c->xkv_windows = rows.plane;
+        c->xmap = rows.wmap ? c->xmap_d : nullptr;
+        auto one_step = [&] {
+            decoder_step(c, nb, 1, false, nullptr);
+            launch_align_tail(c->logits, nb, V, eot, ctx, pos, A.slot, A.len, A.head, A.forced, A.tokprob, cur_tok, sel,
+                              c->stream);
+            launch_align_bump(pos, c->stream);
+        };
+        const int CH = 8;
+        hipGraphExec_t ge = nullptr;
+        // its own key (no decode key starts below 1), with what shapes the launches: the rows, the
+        // buffers' generation, the score stride, the cross-K/V plane stride, whether the rows read
+        // it through the map and whose row state they write (the map's contents and the forced
+        // tokens are data: another call of the same shape on other slots replays the graph)
+        if (c->use_graph && !c->prof_eager && pmax >= CH)
+            ge = decode_graph(c, {-77, nb, A.gen, pstride, eot, rows.plane, rows.wmap ? 1 : 0, rows.own ? 1 : 0},
+                              one_step, CH);
+        for (int steps = 0; steps < pmax;) {
+            if (ge && pmax - steps >= CH) {
+                HIPCHK(hipGraphLaunch(ge, c->stream));
+                steps += CH;
+            } else {
+                one_step();
+                steps += 1;
+            }
+            HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipGetLastError());
     }
-    c->acap = nullptr;
     launch_align_post(A.scores, ns, A.n_heads, pstride, c->T, A.slot_len, A.slot_head, A.slot_frames, A.slot_width, A.stats,
                       A.colstats, A.M, c->stream);
     launch_align_dtw(A.M, (int64_t)pstride * c->T, c->T, 1, ns, A.slot_T, A.slot_frames, A.trace,
@@ -756,11 +820,30 @@ void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
     HIPCHK(hipMemcpyAsync(tp.data(), A.tokprob, tp.size() * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     for (int i = 0; i < n; ++i) {
-        const int sl = slot[w[i].window];
+        const int sl = slot[P.row[i]];
         if (sl < 0) continue;
         for (int k = 0; k <= w[i].n_tokens; ++k) r->token_frame[(size_t)i * r->stride + k] = tf[(size_t)sl * ctx + k];
         for (int k = 0; k < w[i].n_tokens; ++k) r->token_prob[(size_t)i * r->stride + k] = std::exp((double)tp[(size_t)sl * ctx + k]);
     }
+}
+
+// osw_align_windows: over the resident cross-K/V of the last encode call, one decoder row per
+// encoded window, on the context's own row state.
+void align(osw_ctx* c, int n, const osw_align_window* w, osw_align_result* r) {
+    const int nb = c->n_encoded;
+    REQUIRE(nb >= 1 && nb <= c->R, "no encoded windows are resident (encode or decode first)");
+    REQUIRE(n <= nb, "more windows than the last encode call holds");
+    const AlignPack P = align_pack(c, n, w, r, nb, false);
+    align_core(c, P, nb, AlignRows{false, nullptr, 0}, n, w, r);
+}
+
+// osw_session_align: n held windows of an open session, entry i in session slot slots[i] (distinct,
+// below max_batch).  One decoder row per entry; the rows that are still decoding keep their state.
+void align_held(osw_ctx* c, int n, const int* slots, const osw_align_window* w, osw_align_result* r) {
+    REQUIRE(n >= 1 && n <= c->B, "more windows than the session has slots");
+    for (int i = 0; i < n; ++i) REQUIRE(slots[i] >= 0 && slots[i] < c->B, "session slot out of range");
+    const AlignPack P = align_pack(c, n, w, r, n, true);
+    align_core(c, P, n, AlignRows{true, slots, c->B}, n, w, r);
 }
 
 // ------------------------------ mel ----------------------------------------

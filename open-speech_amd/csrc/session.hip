@@ -1,6 +1,7 @@
 // Decode sessions (osw_session_*): the resident clip store, admission, the chunked step and the
 // session entry points of the C ABI.
 #include "ctx.h"
+#include "slots.h"
 
 // ------------------------------ decode sessions ------------------------------
 // Continuous batching (osw_session_*, include/osw.h): c->B window slots, `beam` decoder rows
@@ -9,6 +10,8 @@
 // keep their full-capacity layouts (ctx->kv_rows, ctx->xkv_windows), so a step may cover only
 // the rows up to the highest occupied slot.  Windows are admitted between chunks of CH steps:
 // their log-mel, their encoder straight into the slots' cross-K/V, then the rows' reset.
+// With osw_session_hold a finished window keeps its slot (slots.h) until osw_session_align has
+// run the word-timing pass over its cross-K/V or osw_session_release has let it go.
 struct SessionWin {
     int64_t clip;            // ClipStore key (a private key < 0 for a window that brought its own PCM)
     std::vector<int> prefix;
@@ -42,9 +45,8 @@ struct ClipStore {
 struct Session {
     DecodePlan plan;  // session-wide: beam, start sequence (plan.P positions), max_length, history rules
     int W = 0;
-    std::vector<int64_t> slot_tag;
+    SlotTable slots;  // free / decoding / held, and the tags
     std::deque<SessionWin> queue;
-    int active = 0;
     int64_t steps = 0;
 };
 
@@ -180,7 +182,7 @@ void session_begin(osw_ctx* c, const osw_decode_opts* o) {
     park_rows(c, R);
     HIPCHK(hipMemsetAsync(c->budget, 0, (size_t)R * 4, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    S->slot_tag.assign(S->W, -1);
+    S->slots = SlotTable(S->W);
     c->row_pos = true;
     c->kv_rows = c->R;
     c->xkv_windows = c->B;
@@ -205,6 +207,11 @@ void session_add(osw_ctx* c, const int16_t* pcm, const int64_t* offsets, int n, 
     // every window is checked before any is queued or any clip registered
     ClipStore& cs = clip_store(c);
     std::map<int64_t, int64_t> fresh;  // caller keys registered by this call -> window index
+    for (int i = 0; i < n && S->slots.hold; ++i) {  // held windows are named by tag: one window per tag
+        REQUIRE(!S->slots.tag_in_use(w[i].tag), "hold: a window of this tag is still decoding or held");
+        for (const SessionWin& q : S->queue) REQUIRE(q.w.tag != w[i].tag, "hold: a window of this tag is queued");
+        for (int j = 0; j < i; ++j) REQUIRE(w[j].tag != w[i].tag, "hold: a tag appears twice");
+    }
     for (int i = 0; i < n; ++i) {
         REQUIRE(offsets[i + 1] >= offsets[i], "offsets must not decrease");
         REQUIRE(w[i].segment_size >= 1 && w[i].seek >= 0, "empty window");
@@ -225,6 +232,7 @@ void session_add(osw_ctx* c, const int16_t* pcm, const int64_t* offsets, int n, 
         // (log_mel's frame count: one frame per 160 samples, plus one)
         if (samples >= 0) REQUIRE(w[i].seek < (int)((samples + 160) / 160), "window seek out of range");
     }
+    S->slots.note_add();
     for (int i = 0; i < n; ++i) {
         SessionWin q;
         if (w[i].clip >= 0) {
@@ -243,12 +251,10 @@ void session_add(osw_ctx* c, const int16_t* pcm, const int64_t* offsets, int n, 
 
 void session_admit(osw_ctx* c, int refill_min) {
     Session* S = c->sess;
-    std::vector<int> free_slots;
-    for (int i = 0; i < S->W; ++i)
-        if (S->slot_tag[i] < 0) free_slots.push_back(i);
+    const std::vector<int> free_slots = S->slots.free_slots();  // (never a held one)
     const int queued = (int)S->queue.size();
     if (!queued || free_slots.empty()) return;
-    if (S->active > 0 && (int)free_slots.size() < std::min(std::max(1, refill_min), queued)) return;
+    if (S->slots.decoding > 0 && (int)free_slots.size() < std::min(std::max(1, refill_min), queued)) return;
     const int k = std::min((int)free_slots.size(), queued);
     // the admitted windows' frames, staged from their clips' resident log-mel as k "clips"
     // (window i = its frames [seek, seek + min(segment, frames - seek)) and its clip's max), so
@@ -294,7 +300,7 @@ void session_admit(osw_ctx* c, int refill_min) {
         S->plan.ss.tokens(q.w.language_token, e + 3 + np);
     }
     encode(c, wins.data(), k, slots.data());
-    for (int i = 0; i < k; ++i) S->slot_tag[free_slots[i]] = S->queue[i].w.tag;
+    for (int i = 0; i < k; ++i) S->slots.admit(free_slots[i], S->queue[i].w.tag);
     HIPCHK(hipMemcpyAsync(c->refill_pack, pack.data(), pack.size() * 4, hipMemcpyHostToDevice, c->stream));
     launch_session_rows(c->refill_pack, k, ps, beam, ctx, ctx, c->prompt, c->budget, c->cur_tok, c->pos, c->sel,
                         beam > 1 ? c->anc : nullptr, beam > 1 ? c->bwin : nullptr, c->stream);
@@ -303,7 +309,6 @@ void session_admit(osw_ctx* c, int refill_min) {
         if (S->queue.front().clip < 0) store_release(c, S->queue.front().clip);  // (its frames were staged)
         S->queue.pop_front();
     }
-    S->active += k;
 }
 
 // returns the number of finished windows written to r / tags
@@ -325,6 +330,9 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
     int done = 0;
     c->conf_res.clear();
     c->conf_valid = c->conf;
+    // every slot held and windows waiting: nothing to launch and nothing to wait for until the
+    // caller aligns or releases (osw_session_align / osw_session_release)
+    if (S->slots.stalled((int)S->queue.size())) return 0;
     if (max_chunks == 0) {  // admission only: the queued windows' encoder, waited for
         session_admit(c, refill_min);
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -333,19 +341,15 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
     Readback rb;
     for (int chunk = 0; chunk < max_chunks && done == 0; ++chunk) {
         session_admit(c, refill_min);
-        if (S->active == 0) break;
-        int hi = 0;
-        for (int i = 0; i < S->W; ++i)
-            if (S->slot_tag[i] >= 0) hi = i + 1;
+        if (S->slots.decoding == 0) break;
+        int hi = S->slots.decoding_end();
         if (hi > 4) hi = std::min(S->W, (hi + 3) / 4 * 4);  // (fewer graph shapes; idle slots' rows are finished)
         const int nb = hi * beam;
         run_chunk(c, plan, nb, hi, CH, c->use_graph && !c->prof_eager);
         S->steps += CH;
-        for (int slot : finished_windows(c, plan, nb, hi, [&](int i) { return S->slot_tag[i] >= 0; }, rb)) {
+        for (int slot : finished_windows(c, plan, nb, hi, [&](int i) { return S->slots.is_decoding(i); }, rb)) {
             write_window(c, plan, r, done, rb, (size_t)slot * beam, slot);
-            tags[done] = S->slot_tag[slot];
-            S->slot_tag[slot] = -1;
-            --S->active;
+            tags[done] = S->slots.finish(slot);  // (hold: the slot and its cross-K/V stay)
             ++done;
         }
     }
@@ -391,9 +395,43 @@ int osw_session_step(osw_ctx* c, int32_t max_chunks, int32_t refill_min, osw_win
         DeviceScope dev_scope_((c->device));
         LaneCall call_(c);
         *n_done = session_step(c, std::max(0, max_chunks), refill_min, res, tags_out, cap);
-        *n_active = c->sess->active;
+        *n_active = c->sess->slots.decoding;
         *n_queued = (int32_t)c->sess->queue.size();
         resolve_events(c);
+    });
+}
+
+int osw_session_hold(osw_ctx* c, int32_t enable) {
+    return guard([&] {
+        REQUIRE(c, "null ctx");
+        std::lock_guard<std::mutex> lk(c->mu);
+        if (!c->sess) throw OswError(OSW_ESTATE, "osw_session_hold: no decode session open");
+        c->sess->slots.set_hold(enable != 0);
+    });
+}
+
+int osw_session_align(osw_ctx* c, int32_t n, const int64_t* tags, const osw_align_window* w, osw_align_result* res) {
+    return guard([&] {
+        REQUIRE(c, "null ctx");
+        std::lock_guard<std::mutex> lk(c->mu);
+        REQUIRE(c->sess, "no decode session open");
+        REQUIRE(n >= 1 && tags && w && res, "null align argument");
+        DeviceScope dev_scope_((c->device));
+        LaneCall call_(c);
+        // every check (tags here, the windows in align_held) comes before the first launch and
+        // before any slot changes: a refused call leaves the session as it was
+        const std::vector<int> slots = c->sess->slots.held_slots(n, tags);
+        align_held(c, n, slots.data(), w, res);
+        c->sess->slots.take_held(slots);
+    });
+}
+
+int osw_session_release(osw_ctx* c, int32_t n, const int64_t* tags) {
+    return guard([&] {
+        REQUIRE(c, "null ctx");
+        std::lock_guard<std::mutex> lk(c->mu);
+        REQUIRE(c->sess, "no decode session open");
+        c->sess->slots.take_held(c->sess->slots.held_slots(n, tags));
     });
 }
 

@@ -418,17 +418,21 @@ class WhisperEngine:
         return self._outputs(n, bufs, dump, cfg.confidences)
 
     # ------------------------------------------------------------ decode sessions
-    def session_begin(self, cfg: DecodeConfig) -> None:
+    def session_begin(self, cfg: DecodeConfig, hold: bool = False) -> None:
         """Open a continuous-batching decode session (osw_session_begin): windows added
         with ``session_add`` are admitted into free decoder slots between chunks of
         decoder steps, each with its own clip, seek, prefix and language.  Temperature 0
         only (greedy or beam search, beam_size <= 5); ``cfg.token_budget`` is per window
-        (``session_add``), not here."""
+        (``session_add``), not here.  ``hold`` (osw_session_hold, word timestamps): a window
+        ``session_step`` returns keeps its slot and cross-K/V until ``session_align`` or
+        ``session_release`` names its tag."""
         o, keep = self._opts(dataclasses.replace(cfg, token_budget=None), 0, None)
         self._set_confidences(cfg.confidences)  # (the session keeps the setting it begins with)
         self._sess_conf = bool(cfg.confidences)
         _lib.check(self.lib.osw_session_begin(self.ctx, C.byref(o)), "osw_session_begin")
         del keep
+        if hold:
+            self.session_hold(True)
         self._sess_res = self._result(self.max_batch, 0)
         self._sess_tags = np.zeros(self.max_batch, np.int64)
 
@@ -470,6 +474,28 @@ class WhisperEngine:
         outs = self._outputs(nd.value, bufs, None, getattr(self, "_sess_conf", False))
         return [(int(self._sess_tags[i]), outs[i]) for i in range(nd.value)], na.value, nq.value
 
+    def session_hold(self, enable: bool = True) -> None:
+        """osw_session_hold: only between ``session_begin`` and the first ``session_add``."""
+        _lib.check(self.lib.osw_session_hold(self.ctx, 1 if enable else 0), "osw_session_hold")
+
+    def session_align(self, windows: list) -> list:
+        """osw_session_align: ``[(tag, AlignWindow)]`` of held windows (``AlignWindow.window`` is
+        ignored) -> one ``Alignment`` each, bit for bit ``align``'s after a batched decode; their
+        slots are free afterwards.  ``alignment_matrix(i)`` then returns entry i's M."""
+        if not windows:
+            return []
+        tags = np.ascontiguousarray([int(t) for t, _ in windows], dtype=np.int64)
+        return self._align([w for _, w in windows], lambda n, arr, res: _lib.check(
+            self.lib.osw_session_align(self.ctx, n, tags.ctypes.data_as(C.POINTER(C.c_int64)), arr, res),
+            "osw_session_align"))
+
+    def session_release(self, tags) -> None:
+        """osw_session_release: free held windows' slots without aligning them."""
+        tags = np.ascontiguousarray([int(t) for t in tags], dtype=np.int64)
+        if len(tags):
+            _lib.check(self.lib.osw_session_release(self.ctx, len(tags), tags.ctypes.data_as(C.POINTER(C.c_int64))),
+                       "osw_session_release")
+
     def session_release_clip(self, clip: int) -> None:
         _lib.check(self.lib.osw_session_release_clip(self.ctx, int(clip)), "osw_session_release_clip")
 
@@ -490,6 +516,10 @@ class WhisperEngine:
         cross-K/V resident from the last encode / decode call; one ``Alignment`` each."""
         if not windows:
             return []
+        return self._align(windows, lambda n, arr, res: _lib.check(
+            self.lib.osw_align_windows(self.ctx, n, arr, res), "osw_align_windows"))
+
+    def _align(self, windows: list, call) -> list:
         st = self.st
         stride = max(len(w.tokens) for w in windows) + 1
         toks = [np.ascontiguousarray(w.tokens if len(w.tokens) else [0], dtype=np.int32) for w in windows]
@@ -506,13 +536,14 @@ class WhisperEngine:
         tp = np.zeros((len(windows), stride), np.float64)
         res = _lib.osw_align_result(token_frame=_i32p(tf), token_prob=tp.ctypes.data_as(C.POINTER(C.c_double)),
                                     stride=stride)
-        _lib.check(self.lib.osw_align_windows(self.ctx, len(windows), arr, C.byref(res)), "osw_align_windows")
+        call(len(windows), arr, C.byref(res))
         del toks
         return [Alignment(tf[i, :len(w.tokens) + 1].copy() if len(w.tokens) else np.zeros(0, np.int32),
                           tp[i, :len(w.tokens)].copy()) for i, w in enumerate(windows)]
 
     def alignment_matrix(self, window: int) -> np.ndarray:
-        """M [n + 1][F] of ``window`` as the last ``align`` call left it (parity tests)."""
+        """M [n + 1][F] of ``window`` as the last ``align`` call left it, or of entry ``window`` of
+        the last ``session_align`` call (parity tests)."""
         T, F = C.c_int32(), C.c_int32()
         _lib.check(self.lib.osw_get_alignment_matrix(self.ctx, int(window), None, 0, C.byref(T), C.byref(F)),
                    "osw_get_alignment_matrix")

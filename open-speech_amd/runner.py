@@ -44,7 +44,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .dims import check_chunk_length
-from .segments import ClipResult, TranscribeOptions, session_supported, transcribe_clips
+from .segments import (ClipResult, TranscribeOptions, session_supported, transcribe_clips,
+                       word_session_supported)
 from .tokenizer import WhisperTokenizer, get_suppressed_tokens
 
 
@@ -210,7 +211,20 @@ class _SessionLane(_Worker):
     hold (segments.session_supported: temperature > 0 or a fallback ladder, max_new_tokens,
     beam_size > 5)
     run through the batched seek loop of an idle lane.
+
+    Word timestamps (segments.word_session_supported) ride the session too: it is begun with
+    ``hold`` (osw_session_hold), so a finished window keeps its slot and cross-K/V until the
+    lane has split it into segments and either aligned its text tokens (one
+    ``session_align`` call for all the windows of a step) or released it (silence, no text, a
+    failed request).  STT_HIP_WORD_SESSIONS=0 sends such requests through the batched seek
+    loop instead, as does an engine without ``session_align``.
     """
+
+    def _session_ok(self, opts) -> bool:
+        if session_supported(opts):
+            return True
+        return (self.pool.word_sessions and word_session_supported(opts)
+                and hasattr(self.engine, "session_align"))
 
     def _admit(self, key, room: int, idle: bool):
         """('sess', key, reqs) — requests to add to the session (key: the session's, or a
@@ -246,7 +260,7 @@ class _SessionLane(_Worker):
                         # waited max_pace_ms: take requests beside the running encoder
                     if idle:
                         head = dq.items[0]
-                        if not session_supported(head.opts):
+                        if not self._session_ok(head.opts):
                             k = head.opts.key()
                             batch = [r for r in dq.items if r.opts.key() == k][:self.engine.max_batch]
                             for r in batch:
@@ -279,11 +293,14 @@ class _SessionLane(_Worker):
                 dq.cv.wait()
 
     def run(self) -> None:
-        from .segments import clip_state, consume_window, finish_clip, next_window, session_config
+        from .segments import (align_request, apply_window, clip_state, consume_window, finish_clip, next_window,
+                               pad_alignment, plan_window, session_config)
         pool, eng, tok = self.pool, self.engine, self.pool.tokenizer
         flights: dict = {}      # tag -> [req, clip state, window]
         key, is_open, tag = None, False, 0
         added = False           # windows queued since the last admission
+        words = False           # the open session holds finished windows for word timing
+        held: set = set()       # tags of windows a step returned that are neither aligned nor released yet
 
         def answer(t, exc=None):
             req, s, w = flights.pop(t)
@@ -297,6 +314,12 @@ class _SessionLane(_Worker):
                     req.fut.set_result(finish_clip(s, req.opts, tok))
                 else:
                     req.fut.set_exception(exc if exc is not None else RuntimeError("request state lost"))
+            if t in held:
+                # the request ends with its window still held: the slot goes back to the lane (a
+                # refusal here reaches the lane's handler, whose session_end frees it)
+                held.discard(t)
+                if is_open:
+                    eng.session_release([t])
 
         def queue_window(t):
             req, s, _ = flights[t]
@@ -331,7 +354,12 @@ class _SessionLane(_Worker):
                     continue
                 _, k, reqs = got
                 if reqs and not is_open:
-                    eng.session_begin(session_config(reqs[0].opts, pool.suppress_for(reqs[0].opts)))
+                    cfg = session_config(reqs[0].opts, pool.suppress_for(reqs[0].opts))
+                    words = bool(reqs[0].opts.word_timestamps)   # (one key per session: all or none)
+                    if words:
+                        eng.session_begin(cfg, hold=True)
+                    else:
+                        eng.session_begin(cfg)
                     key, is_open = k, True
                 for r in reqs:
                     tag += 1
@@ -358,10 +386,40 @@ class _SessionLane(_Worker):
                             self.dq.encoding -= 1
                             self.dq.cv.notify_all()
                 done, _, _ = eng.session_step(max_chunks=1, refill_min=pool.refill_min)
+                if words:
+                    # every window of this step is held: plan each, align the ones with text in one
+                    # call, release the rest, all before the next step; then keep the segments
+                    # (the seek moves to the last word's end) and queue each clip's next window
+                    held.update(t for t, _ in done)
+                    plans, wanted = {}, []
+                    for t, out in done:
+                        req, s, w = flights[t]
+                        try:
+                            plans[t] = plan_window(s, w, out, req.opts, tok)
+                            aw = align_request(plans[t], w, out, req.opts, tok)
+                            if aw is not None:
+                                wanted.append((t, aw))
+                        except Exception as e:  # noqa: BLE001
+                            if pool.is_device_error(e):
+                                raise
+                            plans.pop(t, None)
+                            answer(t, e)        # (releases the held window)
+                    als = eng.session_align(wanted) if wanted else []
+                    held.difference_update(t for t, _ in wanted)
+                    aligned = {t: pad_alignment(a, plans[t]) for (t, _), a in zip(wanted, als)}
+                    rest = [t for t, _ in done if t in held]
+                    if rest:
+                        eng.session_release(rest)
+                        held.difference_update(rest)
                 for t, out in done:
+                    if t not in flights:
+                        continue
                     req, s, w = flights[t]
                     try:
-                        consume_window(s, w, out, req.opts, tok)
+                        if not words:
+                            consume_window(s, w, out, req.opts, tok)
+                        elif plans[t] is not None:
+                            apply_window(s, w, out, req.opts, tok, plans[t], aligned.get(t))
                         queue_window(t)
                     except Exception as e:  # noqa: BLE001
                         if pool.is_device_error(e):
@@ -378,6 +436,7 @@ class _SessionLane(_Worker):
                     if not any(r is q for q in reqs):
                         reqs.append(r)
                 flights.clear()
+                held.clear()            # (session_end frees what is still held)
                 added = False
                 if is_open:
                     try:
@@ -432,6 +491,9 @@ class BatchRunner:
         # encodes; STT_HIP_BUSY_ADMIT=0: never (the round-5 pacing, for A/B runs)
         import os
         self.busy_admit = os.environ.get("STT_HIP_BUSY_ADMIT", "1") != "0"
+        # word-timestamp requests ride the decode sessions (hold / align / release);
+        # STT_HIP_WORD_SESSIONS=0: the batched seek loop of an idle lane, for A/B runs
+        self.word_sessions = os.environ.get("STT_HIP_WORD_SESSIONS", "1") != "0"
         self._sup_cache: dict = {}
         self._lock = threading.Lock()
         self.queues: list[_DevQueue] = []

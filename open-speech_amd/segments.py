@@ -486,6 +486,17 @@ def session_supported(opts: TranscribeOptions) -> bool:
     return len(temps) == 1 and not (temps[0] > 0) and opts.max_new_tokens is None and 1 <= int(opts.beam_size) <= 5
 
 
+def word_session_supported(opts: TranscribeOptions) -> bool:
+    """Word timing on a decode session (osw_session_hold / osw_session_align): a request with
+    ``word_timestamps`` whose other options a session can hold.  ``session_supported`` itself
+    keeps answering False for it: a driver without the hold / align calls must leave such a
+    request to the batched seek loop."""
+    if not opts.word_timestamps:
+        return False
+    import dataclasses
+    return session_supported(dataclasses.replace(opts, word_timestamps=False))
+
+
 def session_config(opts: TranscribeOptions, suppress: tuple) -> DecodeConfig:
     """The session-wide decode configuration (transcribe_clips' per-call one, minus the
     per-window prefix, language and token budget)."""
@@ -525,6 +536,36 @@ def next_window(s: _ClipState, opts: TranscribeOptions, tok: WhisperTokenizer) -
 
 def consume_window(s: _ClipState, win: dict, out, opts: TranscribeOptions, tok: WhisperTokenizer) -> None:
     _consume(s, (s.idx, win["seek"], win["segment_size"]), out, opts, tok)
+
+
+def plan_window(s: _ClipState, win: dict, out, opts: TranscribeOptions, tok: WhisperTokenizer):
+    """``consume_window`` in two halves, for word timing on a session: the window's segments before
+    they are kept (None: skipped as silence, the seek already moved), with ``text_tokens``."""
+    return _plan(s, (s.idx, win["seek"], win["segment_size"]), out, opts, tok)
+
+
+def align_request(plan, win: dict, out, opts: TranscribeOptions, tok: WhisperTokenizer):
+    """The ``AlignWindow`` of a planned window, as transcribe_clips asks for it (None: nothing to
+    align — a skipped window or one without text tokens).  The forced sequence adds 5 positions
+    (3 for an English-only model): a window that decoded more text tokens than fit aligns the
+    ones that do (``pad_alignment`` covers the rest)."""
+    if plan is None or not plan["text_tokens"]:
+        return None
+    from .engine import AlignWindow
+    room = 448 - (_start_len(tok.special) + 2)
+    return AlignWindow(window=0, tokens=plan["text_tokens"][:room], num_frames=win["segment_size"],
+                       language=out.language, task=opts.task)
+
+
+def pad_alignment(alignment, plan):
+    return _pad_alignment(alignment, len(plan["text_tokens"]))
+
+
+def apply_window(s: _ClipState, win: dict, out, opts: TranscribeOptions, tok: WhisperTokenizer, plan: dict,
+                 alignment) -> None:
+    """Keep a planned window's segments, with their words when ``alignment`` is given; the seek
+    moves to the last word's end as in transcribe_clips."""
+    _apply(s, (s.idx, win["seek"], win["segment_size"]), out, opts, tok, plan, alignment)
 
 
 def finish_clip(s: _ClipState, opts: TranscribeOptions, tok: WhisperTokenizer) -> ClipResult:
