@@ -425,6 +425,41 @@ int osw_session_align(osw_ctx* ctx, int32_t n, const int64_t* tags, const struct
                       struct osw_align_result* res);
 int osw_session_release(osw_ctx* ctx, int32_t n, const int64_t* tags);
 
+/* ---- temperature fallback on a session: retry a held window in place ----
+ * faster-whisper's generate_with_fallback decodes a window again at the next temperature of a
+ * ladder when its text is too repetitive or its average log-probability too low.  A held window
+ * (above) has what a retry needs, its slot and its cross-K/V, so it goes back to decoding where it
+ * is, with best_of sampled rows, beside slots that go on at temperature 0; the encoder does not run.
+ *
+ * osw_session_retries: valid in a hold-mode session, after osw_session_hold(1) and before the
+ * session's first osw_session_add, else OSW_ESTATE (also without an open session).  1 <= best_of
+ * <= 5, else OSW_EINVAL.  The session then keeps max(beam_size, best_of) decoder rows per slot
+ * (the context has 5 x max_batch rows; nothing is allocated per row).  A session that never calls
+ * it runs the statements and launches it ran before.
+ *
+ * osw_session_retry: n held windows decode again.  entries[i].tag names a held window; all tags
+ * held and distinct, every temperature finite and > 0, every language_token inside the vocabulary
+ * (an English-only model ignores it), else OSW_EINVAL; a session without osw_session_retries:
+ * OSW_ESTATE.  A refused call launches nothing and changes nothing.  Each window's slot goes from
+ * held to decoding; its rows restart at step 0 of the prompt it was admitted with (prefix, token
+ * budget; the language position holds language_token: pass the language attempt 0 reported), rows
+ * 0 .. best_of-1 sample at `temperature` with `seed`, the slot's other rows are parked.  When all
+ * its sampled rows have ended, osw_session_step returns the window again, held: the row with the
+ * highest sum_logprob / n_tokens^length_penalty (the first on ties), as osw_decode_windows returns
+ * for temperature > 0.  That result is bit for bit what osw_decode_windows returns for the window
+ * as the first of its call with the same temperature, best_of, seed, prefix, language and token
+ * budget, and every window decoding beside it still decodes as it does alone.  The caller then
+ * retries it again, aligns it or releases it; admission into a released slot puts its rows back
+ * to temperature 0. */
+typedef struct osw_retry_window {
+    int64_t tag;
+    float temperature;
+    uint64_t seed;
+    int32_t language_token;
+} osw_retry_window;
+int osw_session_retries(osw_ctx* ctx, int32_t best_of);
+int osw_session_retry(osw_ctx* ctx, int32_t n, const osw_retry_window* entries);
+
 /* ---- confidences: per-token log-probabilities and language probabilities ----
  * Off by default.  On, every decode entry point (osw_decode_windows, osw_transcribe_batch,
  * osw_transcribe_refill, osw_session_step) also keeps, per returned window, what the token
@@ -611,6 +646,15 @@ typedef struct osw_select_io {
     int32_t* counters;     /* out: [1 + rows] rows finalised, then each row's slice tickets */
 } osw_select_io;
 int osw_debug_select_step(osw_ctx* ctx, const osw_decode_opts* opts, const osw_select_io* io);
+/* The same in OSW_SELECT_SESSION mode for a retry session (osw_session_retries): rows_per_slot =
+ * max(beam_size, best_of) decoder rows per window slot (beam_size <= rows_per_slot <= 5), io->rows a
+ * multiple of it, and the rows' sampling state row_inv_temp[rows] (finite, >= 0) / row_seed[rows].
+ * A slot whose first row holds row_inv_temp > 0 samples on its rows with row_inv_temp > 0 and its
+ * other rows are parked; any other slot steps its first beam_size rows at temperature 0 and the
+ * rest are parked.  Parked rows are neither read nor written.  The beam-window consistency checks
+ * above apply to the temperature-0 slots' first beam_size rows. */
+int osw_debug_select_step_rows(osw_ctx* ctx, const osw_decode_opts* opts, const osw_select_io* io,
+                               int32_t rows_per_slot, const float* row_inv_temp, const uint64_t* row_seed);
 
 /* Parity helper: one encoder block on x [T][D] fp32 (host), result to y (host). */
 int osw_encoder_layer_debug(osw_ctx* ctx, int32_t layer, const float* x, float* y, int32_t T);

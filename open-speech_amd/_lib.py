@@ -75,6 +75,10 @@ _SELECT_ARRAYS = ("logits", "pos", "state", "prompt", "cur_tok", "tokens", "budg
 _SELECT_FLOAT = ("logits", "lp_hist", "best_lp", "lang_probs")
 
 
+class osw_retry_window(C.Structure):
+    _fields_ = [("tag", C.c_int64), ("temperature", C.c_float), ("seed", C.c_uint64), ("language_token", C.c_int32)]
+
+
 class osw_select_io(C.Structure):
     """osw_debug_select_step's arrays: every ``*_len`` counts 32-bit words (include/osw.h)."""
     ARRAYS, FLOAT = _SELECT_ARRAYS, _SELECT_FLOAT
@@ -133,6 +137,9 @@ _SIGS = {
     "osw_session_hold": (C.c_int, [C.c_void_p, C.c_int32]),
     "osw_session_align": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_int64), P(osw_align_window), P(osw_align_result)]),
     "osw_session_release": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_int64)]),
+    # temperature fallback on a session: a held window decodes again in its slot with sampled rows
+    "osw_session_retries": (C.c_int, [C.c_void_p, C.c_int32]),
+    "osw_session_retry": (C.c_int, [C.c_void_p, C.c_int32, P(osw_retry_window)]),
     # confidences (replace ctranslate2's return_scores per token, faster-whisper's language_probability /
     # all_language_probs and WhisperModel.detect_language)
     "osw_set_confidences": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -166,6 +173,8 @@ _SIGS = {
                                                C.c_int32, P(C.c_float)]),
     # one selection step (select kernel + beam update) on host logits and state (tests/test_gpu_select.py)
     "osw_debug_select_step": (C.c_int, [C.c_void_p, P(osw_decode_opts), P(osw_select_io)]),
+    "osw_debug_select_step_rows": (C.c_int, [C.c_void_p, P(osw_decode_opts), P(osw_select_io), C.c_int32,
+                                             P(C.c_float), P(C.c_uint64)]),
     "osw_encoder_layer_debug": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_float), C.c_int32]),
     "osw_debug_gemm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                  P(C.c_float), C.c_int32, P(C.c_float)]),

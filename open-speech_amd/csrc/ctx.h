@@ -308,6 +308,17 @@ struct osw_ctx {
     int* sel_arrive = nullptr; // select arrival counters: rows finalised + per-row slice tickets (zero between launches)
     int* budget = nullptr;     // per-row token budgets (osw_decode_opts::token_budget)
     unsigned long long* seed_d = nullptr;  // sampling seed of the current decode call
+    // Retry sessions (osw_session_retries), allocated by the context's first one: the rows' sampling
+    // state (SelParams::row_inv_temp / row_seed), the admission / retry pack, and for a greedy
+    // session with best_of > 1 (xsplit) the second cross-attention launch's done-flag copies,
+    // row -> slot map and tickets (decode_host.hip step_cross_attn)
+    float* row_inv_temp = nullptr;             // [R]
+    unsigned long long* row_seed = nullptr;    // [R]
+    int* retry_pack = nullptr;                 // [B][RETRY_PACK_HEAD + n_text_ctx]
+    SelState *xdone_single = nullptr, *xdone_group = nullptr;  // [R]
+    int* xrow_map = nullptr;                   // [R]
+    int* xrow_ticket = nullptr;                // [R][H] (zero between launches)
+    bool xsplit = false;                       // the open session is a greedy retry session with best_of > 1
     int64_t part_floats = 0;
 
     // decode-step graphs (CH steps per replay), one per key (batch rows, prompt length,
@@ -419,17 +430,22 @@ struct Readback {
     std::vector<BeamWin> bw;
     std::vector<int> toks;
     std::vector<float> cum, lang;
+    std::vector<int> rtoks;   // a beam retry session: the rows' own tokens / cumulative log-probs,
+    std::vector<float> rcum;  // read when a sampling slot finished
 };
 void bind_plan(osw_ctx* c, DecodePlan& p, const osw_decode_opts* o);
 void plan_select(osw_ctx* c, const DecodePlan& p, int rows, int windows);
 void run_chunk(osw_ctx* c, const DecodePlan& p, int rows, int windows, int CH, bool graph,
                const SelFuse* sf = nullptr);
 std::vector<int> finished_windows(osw_ctx* c, const DecodePlan& p, int rows, int windows,
-                                  const std::function<bool(int)>& live, Readback& rb);
+                                  const std::function<bool(int)>& live, Readback& rb,
+                                  const std::function<int(int)>& armed = nullptr);
+size_t best_sample(const Readback& rb, size_t first, int n, float length_penalty);
 void park_rows(osw_ctx* c, int R);
 void write_window(osw_ctx* c, const DecodePlan& p, osw_window_result* r, size_t out, const Readback& rb, size_t row,
-                  size_t win);
+                  size_t win, bool sampled = false);
 
 // session.hip
+void retry_reserve(osw_ctx* c);     // the context's retry-session buffers (osw_ctx::row_inv_temp ...), once
 void session_destroy(osw_ctx* c);  // the open session and the clip store, at osw_destroy
 }  // namespace osw

@@ -145,11 +145,21 @@ int osw_debug_history_rules_time(osw_ctx* c, int32_t rows, int32_t V, int32_t n_
 // One selection step on host state (osw.h osw_debug_select_step): the plan the decode paths
 // build, bound to the context's buffers, one plan_select.  Everything a kernel indexes with is
 // checked here first; the row modes restate select.h sel_mode on the host.
-int osw_debug_select_step(osw_ctx* c, const osw_decode_opts* o, const osw_select_io* io) {
+// rows_per_slot > 0 (osw_debug_select_step_rows): the plan of a retry session with that many rows
+// per slot and the rows' sampling state, so the launches are a retry session's.
+static int select_step(osw_ctx* c, const osw_decode_opts* o, const osw_select_io* io, int rows_per_slot,
+                       const float* row_inv_temp, const uint64_t* row_seed) {
     return guard([&] {
         static_assert(sizeof(SelState) == 40 && sizeof(BeamWin) == 24, "the word layouts osw.h documents");
         REQUIRE(c && o && io, "null argument");
         REQUIRE(io->mode >= OSW_SELECT_BATCH && io->mode <= OSW_SELECT_SESSION, "select step: unknown mode");
+        const bool retry = rows_per_slot > 0;
+        if (retry) {
+            REQUIRE(io->mode == OSW_SELECT_SESSION, "select step: row temperatures belong to session mode");
+            REQUIRE(row_inv_temp && row_seed, "select step: null row temperatures / seeds");
+            REQUIRE(rows_per_slot <= 5 && rows_per_slot >= std::max(1, o->beam_size) && o->beam_size <= 5,
+                    "select step: beam_size <= rows_per_slot <= 5");
+        }
         std::lock_guard<std::mutex> lk(c->mu);
         DeviceScope dev_scope_((c->device));
         REQUIRE(!c->sess, "select step: a decode session is open");
@@ -164,7 +174,7 @@ int osw_debug_select_step(osw_ctx* c, const osw_decode_opts* o, const osw_select
         oo.prefix_tokens = io->prompt;
         oo.token_budget = io->budget;
         oo.language_tokens = nullptr;
-        DecodePlan plan(mode, &oo, d, oo.n_prefix);
+        DecodePlan plan(mode, &oo, d, oo.n_prefix, 0, rows_per_slot);
         const SelParams& sp = plan.sp;
         const int rows = io->rows, group = plan.group, K = plan.beam, max_tok = plan.max_tok, pstride = sp.pstride;
         REQUIRE(rows >= 1 && rows % group == 0 && rows <= c->R, "select step: rows must be a multiple of the group, at most the row capacity");
@@ -203,6 +213,7 @@ int osw_debug_select_step(osw_ctx* c, const osw_decode_opts* o, const osw_select
         for (int r = 0; r < rows; ++r) {
             const SelState& s = st[r];
             const int step = io->pos[per_row ? r : 0];
+            if (retry) REQUIRE(std::isfinite(row_inv_temp[r]) && row_inv_temp[r] >= 0.f, "select step: bad row temperature");
             REQUIRE(step >= 0 && step < ctx, "select step: step counter outside [0, n_text_ctx)");
             if (mode == DecodeMode::Session)
                 REQUIRE(s.plen >= sp.tail && s.plen < sp.max_length && s.plen <= pstride, "select step: plen out of range");
@@ -224,7 +235,9 @@ int osw_debug_select_step(osw_ctx* c, const osw_decode_opts* o, const osw_select
             if (step >= pl - 1 && !s.done)
                 REQUIRE(step == pl - 1 + s.n_sampled, "select step: a sampling row's counter is not plen - 1 + n_sampled");
             if (!beam) continue;
-            const int r0 = r - r % K;
+            // (a retry session: the checks below hold for the first K rows of a temperature-0 slot)
+            if (retry && (row_inv_temp[r - r % group] > 0.f || r % group >= K)) continue;
+            const int r0 = r - r % group;
             const SelState& s0 = st[r0];
             REQUIRE(s.n_sampled == s0.n_sampled && s.plen == s0.plen && (s.done != 0) == (s0.done != 0) &&
                         step == io->pos[per_row ? r0 : 0],
@@ -235,6 +248,7 @@ int osw_debug_select_step(osw_ctx* c, const osw_decode_opts* o, const osw_select
             }
         }
         // the state up, one selection, everything back
+        if (retry) retry_reserve(c);
         bind_plan(c, plan, &oo);
         auto up = [&](void* dst, const void* src, int64_t words) {
             HIPCHK(hipMemcpyAsync(dst, src, (size_t)words * 4, hipMemcpyHostToDevice, c->stream));
@@ -258,6 +272,10 @@ int osw_debug_select_step(osw_ctx* c, const osw_decode_opts* o, const osw_select
         if (conf) up(c->lp_hist, io->lp_hist, (int64_t)rows * ctx);
         if (conf && beam) up(c->best_lp, io->best_lp, (int64_t)windows * ctx);
         if (langp) up(c->lang_probs, io->lang_probs, (int64_t)windows * sp.n_langs);
+        if (retry) {
+            up(c->row_inv_temp, row_inv_temp, rows);
+            up(c->row_seed, row_seed, (int64_t)rows * 2);
+        }
         plan_select(c, plan, rows, windows);
         HIPCHK(hipGetLastError());
         if (plan.hr.on) down(io->logits, c->logits, (int64_t)rows * V);
@@ -276,6 +294,16 @@ int osw_debug_select_step(osw_ctx* c, const osw_decode_opts* o, const osw_select
         down(io->counters, c->sel_arrive, 1 + rows);
         HIPCHK(hipStreamSynchronize(c->stream));
     });
+}
+
+int osw_debug_select_step(osw_ctx* c, const osw_decode_opts* o, const osw_select_io* io) {
+    return select_step(c, o, io, 0, nullptr, nullptr);
+}
+
+int osw_debug_select_step_rows(osw_ctx* c, const osw_decode_opts* o, const osw_select_io* io, int32_t rows_per_slot,
+                               const float* row_inv_temp, const uint64_t* row_seed) {
+    if (rows_per_slot < 1) return guard([] { REQUIRE(false, "select step: rows_per_slot must be >= 1"); });
+    return select_step(c, o, io, rows_per_slot, row_inv_temp, row_seed);
 }
 
 int osw_encoder_layer_debug(osw_ctx* c, int32_t layer, const float* x, float* y, int32_t T) {

@@ -33,6 +33,15 @@ constexpr int XCHUNKS = 8;    // fixed key chunks per (window, head) in cross-at
 
 void launch_session_rows(const int* pack, int k, int ps, int group, int pstride, int ctx, int* prompt, int* budget,
                          int* cur_tok, int* pos, SelState* st, int* anc, BeamWin* bwin, hipStream_t s);
+// Retry sessions (osw_session_retries): the rows of admitted or retried slots with their sampling
+// state, pack stride ps = RETRY_PACK_HEAD + ctx (decode.hip session_retry_rows_kernel); and the two
+// done-flag copies a greedy retry session's two cross-attention launches read
+constexpr int RETRY_PACK_HEAD = 8;
+void launch_session_retry_rows(const int* pack, int k, int ps, int group, int pstride, int ctx, int* prompt,
+                               int* budget, int* cur_tok, int* pos, SelState* st, int* anc, BeamWin* bwin,
+                               float* row_inv_temp, unsigned long long* row_seed, hipStream_t s);
+void launch_retry_xmask(const SelState* st, const float* row_inv_temp, int group, int rows, SelState* single,
+                        SelState* grouped, hipStream_t s);
 void launch_refill_rows(const int* pack, int k, int P, int* prompt, int* budget, int* cur_tok, int* pos, SelState* st,
                         hipStream_t s);
 void launch_select(const float* logits, int rows, int* pos, const SelParams& P, const int* prompt,

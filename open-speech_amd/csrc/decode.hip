@@ -920,7 +920,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void s
             return;
         }
     }
-    select_partial_body<MODE == 1>(logits, P, step, supmask, st, parts);
+    select_partial_body<MODE == 1>(logits, P, step, supmask, st, parts, blockIdx.x);
     __shared__ int last;
     __shared__ SelPart rp[SEL_SPLIT];
     const int b = blockIdx.x;
@@ -948,6 +948,63 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void s
         __hip_atomic_store(arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(pos_ptr, step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+
+// The selection of a retry session (osw_session_retries; SelParams::row_inv_temp / row_seed):
+// select_kernel's grid, tickets and finaliser, with the row's path chosen per launch from data.
+//   a slot whose first row has row_inv_temp > 0 samples: each of its rows with row_inv_temp > 0
+//     takes select_kernel<1>'s path with its own 1 / temperature and seed (Q below is P with
+//     those and beam 1, so the finaliser picks the row's token whatever the session's beam; the
+//     hash's row argument is the row's index in its slot), at every sampled step, the one at
+//     plen - 1 included; its other rows are parked: nothing is read or written for them
+//   any other slot decodes at temperature 0 on its first P.beam rows: select_kernel<0>'s path,
+//     or (BEAM) select_kernel<2>'s; the rest of its lp_group rows are parked
+// The same functions on the same operands as those kernels, so a row's state after the step
+// is what they leave.  `bump` (greedy sessions): a finalised row advances its own counter; in a
+// beam session beam_update_kernel advances the counters of both kinds of slot.
+template <bool BEAM>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void select_retry_kernel(
+    const float* __restrict__ logits, SelParams P, int* __restrict__ pos_ptr, const unsigned* __restrict__ supmask,
+    const int* __restrict__ prompt, SelPart* __restrict__ parts, SelState* __restrict__ st, int* __restrict__ cur_tok,
+    int* __restrict__ tokens, int max_tokens, int* __restrict__ ticket, int bump, BeamCand* __restrict__ cand) {
+    const int b = blockIdx.x, k = b % P.lp_group;
+    const float inv = P.row_inv_temp[b];
+    const bool samples = P.row_inv_temp[b - k] > 0.f;
+    if (samples ? !(inv > 0.f) : k >= P.beam) return;  // a parked row (the same for every slice)
+    const int step = pos_ptr[b];
+    SelParams Q = P;
+    if (samples) {
+        Q.inv_temp = inv;
+        Q.seed = P.row_seed + b;
+        Q.beam = 1;
+        select_partial_body<true>(logits, Q, step, supmask, st, parts, k);
+    } else {
+        if constexpr (BEAM) {
+            const SelState s = st[b];
+            if (sel_mode(P, step, s) == SEL_SAMPLE) {
+                if (step == row_plen(P, s) - 1 && k != 0) return;  // only the prompt hypothesis expands
+                beam_slice_body<true>(logits, P, step, supmask, s, parts, cand);
+                return;
+            }
+        }
+        select_partial_body<false>(logits, P, step, supmask, st, parts, b);
+    }
+    __shared__ int last;
+    __shared__ SelPart rp[SEL_SPLIT];
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_s_waitcnt(0);  // this slice's part stores are complete at device scope
+        last = __hip_atomic_fetch_add(ticket + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == SEL_SPLIT - 1;
+        if (last) __hip_atomic_store(ticket + b, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // next launch
+    }
+    __syncthreads();
+    if (!last) return;
+    if (threadIdx.x < SEL_SPLIT) rp[threadIdx.x] = load_part(parts + b * SEL_SPLIT + threadIdx.x);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    select_final_row(logits, Q, step, prompt, rp, st, cur_tok, tokens, max_tokens);
+    if (!bump) return;
+    __builtin_amdgcn_s_waitcnt(0);  // every slice of this row has read its counter
+    __hip_atomic_store(pos_ptr + b, step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---------------------------------------------------------------------------
@@ -1070,7 +1127,8 @@ __device__ unsigned long long osw_stamps[32];
     } while (0)
 #endif
 
-template <int KM>
+// GROUPED (retry sessions): a window's rows start at w * lp_group (lp_group >= beam rows per slot)
+template <int KM, bool GROUPED = false>
 __device__ __forceinline__ void beam_update_body(const SelParams& P, const int* __restrict__ pos_ptr,
                                                           SelState* __restrict__ st, const SelPart* __restrict__ parts,
                                                           const BeamCand* __restrict__ cand, int* __restrict__ seq,
@@ -1088,7 +1146,7 @@ __device__ __forceinline__ void beam_update_body(const SelParams& P, const int* 
     __shared__ float ch_score[KM], best_score;
     OSW_STAMP(0);
     const int w = blockIdx.x, tid = threadIdx.x, K = P.beam, K2 = 2 * K;
-    const int r0 = w * K;
+    const int r0 = w * (GROUPED ? P.lp_group : K);
     const int step = pos_ptr[P.pos_row ? r0 : 0];
     const SelState s0 = st[r0];
     const int nc = K * BEAM_SLICES * K2;
@@ -1392,19 +1450,30 @@ __device__ __forceinline__ void beam_update_body(const SelParams& P, const int* 
 // grid windows: the per-window merge / finish / reorder, then an arrival count over
 // the windows; the last one advances the device step counter (every window read it
 // at its start), so beam steps need no separate bump launch.
-template <int KM>
+// RETRY (retry sessions, always per-row counters): rows start at w * lp_group; a window whose
+// rows sample (row_inv_temp of its first row > 0) was finalised by select_retry_kernel, so only
+// its armed rows' counters advance here and its tokens, ancestry and bookkeeping stay untouched.
+template <int KM, bool RETRY = false>
 __global__ __launch_bounds__(256) void beam_update_kernel(SelParams P, int* __restrict__ pos_ptr,
                                                           SelState* __restrict__ st, const SelPart* __restrict__ parts,
                                                           const BeamCand* __restrict__ cand, int* __restrict__ seq,
                                                           int* __restrict__ anc, int ctx, BeamWin* __restrict__ bwin,
                                                           int* __restrict__ best_tok, int* __restrict__ cur_tok,
                                                           int max_tokens, int* __restrict__ arrive) {
-    const int step = pos_ptr[P.pos_row ? blockIdx.x * P.beam : 0];
-    beam_update_body<KM>(P, pos_ptr, st, parts, cand, seq, anc, ctx, bwin, best_tok, cur_tok, max_tokens);
+    const int r0 = blockIdx.x * (RETRY ? P.lp_group : P.beam);
+    if constexpr (RETRY) {
+        if (P.row_inv_temp[r0] > 0.f) {
+            const int r = r0 + threadIdx.x;
+            if (threadIdx.x < P.lp_group && P.row_inv_temp[r] > 0.f) pos_ptr[r] = pos_ptr[r] + 1;
+            return;
+        }
+    }
+    const int step = pos_ptr[P.pos_row ? r0 : 0];
+    beam_update_body<KM, RETRY>(P, pos_ptr, st, parts, cand, seq, anc, ctx, bwin, best_tok, cur_tok, max_tokens);
     __syncthreads();
     OSW_STAMP_LAST(9);
     if (P.pos_row) {  // a session: this window's rows advance their own counters
-        if (threadIdx.x < P.beam) pos_ptr[blockIdx.x * P.beam + threadIdx.x] = step + 1;
+        if (threadIdx.x < P.beam) pos_ptr[r0 + threadIdx.x] = step + 1;
         return;
     }
     if (threadIdx.x != 0) return;
@@ -1455,6 +1524,55 @@ __global__ __launch_bounds__(64) void session_rows_kernel(const int* __restrict_
         st[row] = s;
         if (bwin && blockIdx.y == 0) bwin[slot] = BeamWin{};
     }
+}
+
+// Retry sessions: session_rows_kernel with the rows' sampling state.  pack[i] = {slot, plen,
+// budget, active, bits of 1 / temperature (0: the session's temperature-0 mode), seed low and high
+// word, 0, prompt[0 .. plen)} with stride `ps`.  Rows [0, active) of the slot start at step 0 of
+// the prompt; rows [active, group) are parked (done, never stepped).  Used for admission (the
+// temperature-0 mode) and for osw_session_retry (a held window decodes again, its cross-K/V as
+// the encoder left it).
+__global__ __launch_bounds__(64) void session_retry_rows_kernel(const int* __restrict__ pack, int ps, int group,
+                                                                int pstride, int ctx, int* __restrict__ prompt,
+                                                                int* __restrict__ budget, int* __restrict__ cur_tok,
+                                                                int* __restrict__ pos, SelState* __restrict__ st,
+                                                                int* __restrict__ anc, BeamWin* __restrict__ bwin,
+                                                                float* __restrict__ row_inv_temp,
+                                                                unsigned long long* __restrict__ row_seed) {
+    const int* e = pack + (int64_t)blockIdx.x * ps;
+    const int slot = e[0], plen = e[1], active = e[3];
+    const int row = slot * group + blockIdx.y;
+    for (int j = threadIdx.x; j < plen; j += blockDim.x) prompt[(int64_t)row * pstride + j] = e[8 + j];
+    if (anc)
+        for (int p = threadIdx.x; p < ctx; p += blockDim.x) anc[(int64_t)row * ctx + p] = row;
+    if (threadIdx.x == 0) {
+        const bool armed = (int)blockIdx.y < active;
+        budget[row] = e[2];
+        cur_tok[row] = e[8];
+        pos[row] = 0;
+        SelState s{};
+        s.plen = plen;
+        s.done = armed ? 0 : 1;
+        st[row] = s;
+        row_inv_temp[row] = armed ? __int_as_float(e[4]) : 0.f;
+        row_seed[row] = (unsigned long long)(unsigned)e[5] | ((unsigned long long)(unsigned)e[6] << 32);
+        if (bwin && blockIdx.y == 0) bwin[slot] = BeamWin{};
+    }
+}
+
+// Greedy retry sessions: the cross-attention runs as two launches per layer, the greedy form over
+// single rows for the temperature-0 slots and the row-group form for the sampling slots, so each
+// slot's rows go through the kernel their decode alone goes through.  The launches skip rows by
+// their done flags; these two copies of the flags hide the other kind's rows from each.
+__global__ __launch_bounds__(256) void retry_xmask_kernel(const SelState* __restrict__ st,
+                                                          const float* __restrict__ row_inv_temp, int group, int rows,
+                                                          SelState* __restrict__ single, SelState* __restrict__ grouped) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const bool samples = row_inv_temp[r - r % group] > 0.f;
+    const int done = st[r].done;
+    single[r].done = (done || samples) ? 1 : 0;
+    grouped[r].done = (done || !samples) ? 1 : 0;
 }
 
 __global__ void count_done_kernel(const SelState* st, int B, int* out) {
@@ -1602,6 +1720,17 @@ void launch_select(const float* logits, int rows, int* pos, const SelParams& P, 
     // arrive[0]: rows finalised this step; arrive[1 + row]: the row's slice tickets; cand:
     // the beam rows' candidate lists (beam_slice_body)
     const dim3 grid(rows, SEL_SPLIT);
+    if (P.row_inv_temp) {  // a retry session: rows pick their path from data (select_retry_kernel)
+        if (P.beam > 1)
+            select_retry_kernel<true><<<grid, 256, 0, s>>>(logits, P, pos, supmask, prompt, (SelPart*)sel_parts, st,
+                                                           cur_tok, tokens, max_tokens, arrive + 1, bump ? 1 : 0,
+                                                           (BeamCand*)cand);
+        else
+            select_retry_kernel<false><<<grid, 256, 0, s>>>(logits, P, pos, supmask, prompt, (SelPart*)sel_parts, st,
+                                                            cur_tok, tokens, max_tokens, arrive + 1, bump ? 1 : 0,
+                                                            (BeamCand*)cand);
+        return;
+    }
     // OSW_BEAM_POPS=1 (A/B switch): the beam candidate lists by K2 block-wide pops everywhere
     static const bool pops_only = std::getenv("OSW_BEAM_POPS") != nullptr;
     if (P.beam > 1 && pops_only)
@@ -1621,7 +1750,11 @@ void launch_select(const float* logits, int rows, int* pos, const SelParams& P, 
 void launch_beam(const float* logits, int windows, int* pos, const SelParams& P, const unsigned* supmask,
                  SelState* st, const void* sel_parts, void* cand, int* seq, int* anc, int ctx, BeamWin* bw,
                  int* best_tok, int* cur_tok, int max_tokens, int* arrive, hipStream_t s) {
-    if (P.beam <= 5)
+    if (P.row_inv_temp)  // (retry sessions hold beam_size <= 5)
+        beam_update_kernel<5, true><<<windows, 256, 0, s>>>(P, pos, st, (const SelPart*)sel_parts,
+                                                            (const BeamCand*)cand, seq, anc, ctx, bw, best_tok, cur_tok,
+                                                            max_tokens, arrive);
+    else if (P.beam <= 5)
         beam_update_kernel<5><<<windows, 256, 0, s>>>(P, pos, st, (const SelPart*)sel_parts, (const BeamCand*)cand, seq,
                                                       anc, ctx, bw, best_tok, cur_tok, max_tokens, arrive);
     else
@@ -1634,6 +1767,18 @@ void launch_session_rows(const int* pack, int k, int ps, int group, int pstride,
                          int* cur_tok, int* pos, SelState* st, int* anc, BeamWin* bwin, hipStream_t s) {
     session_rows_kernel<<<dim3(k, group), 64, 0, s>>>(pack, ps, group, pstride, ctx, prompt, budget, cur_tok, pos, st,
                                                       anc, bwin);
+}
+
+void launch_session_retry_rows(const int* pack, int k, int ps, int group, int pstride, int ctx, int* prompt,
+                               int* budget, int* cur_tok, int* pos, SelState* st, int* anc, BeamWin* bwin,
+                               float* row_inv_temp, unsigned long long* row_seed, hipStream_t s) {
+    session_retry_rows_kernel<<<dim3(k, group), 64, 0, s>>>(pack, ps, group, pstride, ctx, prompt, budget, cur_tok, pos,
+                                                            st, anc, bwin, row_inv_temp, row_seed);
+}
+
+void launch_retry_xmask(const SelState* st, const float* row_inv_temp, int group, int rows, SelState* single,
+                        SelState* grouped, hipStream_t s) {
+    retry_xmask_kernel<<<(rows + 255) / 256, 256, 0, s>>>(st, row_inv_temp, group, rows, single, grouped);
 }
 
 void launch_history_rules(float* logits, int rows, const int* pos, const SelParams& P, const SelState* st,

@@ -16,6 +16,30 @@ void align_capture(osw_ctx* c, int l, const float* part, int ks, int nb, int64_t
 }
 
 // ---------------------------- decoder --------------------------------------
+// The step's cross-attention launch.  A greedy retry session (c->xsplit: beam 1, best_of > 1 rows
+// per slot) makes two: a temperature-0 slot decodes on its first row alone and must see what its
+// decode alone sees, the one-row kernel (the row-group kernels round differently), while a
+// sampling slot's rows go through the row-group kernel a batch decode with best_of rows takes.
+// Each launch skips the other kind's rows by its own copy of the done flags (retry_xmask_kernel,
+// once per step); the one-row launch reads each row's slot through a row -> slot map and has its
+// own tickets, one per (row, head).
+namespace {
+bool split_cross_attn(const osw_ctx* c) { return c->xsplit && !c->acap; }
+
+void step_cross_attn(osw_ctx* c, const float* part, int ks, const float* bias, const h16* xk, const h16* xv, int nb,
+                     int H, int group, int64_t lo_d) {
+    if (split_cross_attn(c)) {
+        launch_dec_cross_attn(part, ks, bias, xk, xv, nb, H, c->T, 1, c->dattn, lo_d, c->xws, c->xrow_ticket,
+                              c->xdone_single, c->stream, c->xrow_map);
+        launch_dec_cross_attn(part, ks, bias, xk, xv, nb, H, c->T, group, c->dattn, lo_d, c->xws, c->xticket,
+                              c->xdone_group, c->stream, c->xmap);
+        return;
+    }
+    launch_dec_cross_attn(part, ks, bias, xk, xv, nb, H, c->T, group, c->dattn, lo_d, c->xws, c->xticket, c->sel,
+                          c->stream, c->xmap);
+}
+}  // namespace
+
 // One decoder row (batch-1 latency; PRO_ROWS): the
 // residual+LayerNorm and GELU-reduce kernels are not launched; each runs as the prologue
 // of the projection that consumes it (gemm_skinny_kernel<.., PRO>, resln.h), and the
@@ -94,9 +118,8 @@ void decoder_step_fused(osw_ctx* c, int nb, int group, bool gather, const SelFus
         fused(PRO_RESLN, resln(WF(c, p + ".o.b"), p + ".ln2", false), p + ".xq.w", D, D);
         {
             Timed t(c, CL_XATTN, 2.0 * nb * H * (double)c->T * 64 * 2);
-            launch_dec_cross_attn(ps[last], ks, WF(c, p + ".xq.b"), c->XKV + (2 * l) * xkv_which,
-                                  c->XKV + (2 * l + 1) * xkv_which, nb, H, c->T, group, c->dattn, lo_d, c->xws,
-                                  c->xticket, c->sel, c->stream, c->xmap);
+            step_cross_attn(c, ps[last], ks, WF(c, p + ".xq.b"), c->XKV + (2 * l) * xkv_which,
+                            c->XKV + (2 * l + 1) * xkv_which, nb, H, group, lo_d);
         }
         if (c->acap) align_capture(c, l, ps[last], ks, nb, xkv_which);
         plain(c->dattn, p + ".xo.w", D, D);
@@ -165,6 +188,8 @@ bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf)
         REQUIRE((int64_t)skinny_ksplit(N, K) * nb * N <= c->part_floats, "split-K workspace too small");
         return launch_gemm_skinny_partial(g, c->part, c->stream);
     };
+    if (split_cross_attn(c))
+        launch_retry_xmask(c->sel, c->row_inv_temp, group, nb, c->xdone_single, c->xdone_group, c->stream);
     static const bool no_fuse = getenv("OSW_NO_FUSE") != nullptr;  // A/B switch
     if (nb <= PRO_ROWS && !no_fuse) {
         decoder_step_fused(c, nb, group, gather, nb == 1 ? sf : nullptr);
@@ -198,9 +223,8 @@ bool decoder_step(osw_ctx* c, int nb, int group, bool gather, const SelFuse* sf)
         ks = partial(c->xdn, D, p + ".xq.w", D, D);
         {
             Timed t(c, CL_XATTN, 2.0 * nb * H * (double)c->T * 64 * 2);
-            launch_dec_cross_attn(c->part, ks, WF(c, p + ".xq.b"), c->XKV + (2 * l) * xkv_which,
-                                  c->XKV + (2 * l + 1) * xkv_which, nb, H, c->T, group, c->dattn, lo_d, c->xws,
-                                  c->xticket, c->sel, c->stream, c->xmap);
+            step_cross_attn(c, c->part, ks, WF(c, p + ".xq.b"), c->XKV + (2 * l) * xkv_which,
+                            c->XKV + (2 * l + 1) * xkv_which, nb, H, group, lo_d);
         }
         if (c->acap) align_capture(c, l, c->part, ks, nb, xkv_which);
         ks = partial(c->dattn, D, p + ".xo.w", D, D);
@@ -313,7 +337,9 @@ hipGraphExec_t decode_graph(osw_ctx* c, const std::vector<int64_t>& key, const s
 // on, the recording pointers), the seed and the suppress mask uploaded.
 void bind_plan(osw_ctx* c, DecodePlan& p, const osw_decode_opts* o) {
     c->conf_valid = false;
-    p.bind(c->seed_d, c->budget, c->conf, c->lp_hist, c->best_lp, c->lang_probs);
+    const bool rows = p.best_of > 0;  // a retry session's plan (osw_debug_select_step_rows)
+    p.bind(c->seed_d, c->budget, c->conf, c->lp_hist, c->best_lp, c->lang_probs, rows ? c->row_inv_temp : nullptr,
+           rows ? c->row_seed : nullptr);
     HIPCHK(hipMemcpyAsync(c->seed_d, &o->seed, 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->supmask, p.mask.data(), p.mask.size() * 4, hipMemcpyHostToDevice, c->stream));
 }
@@ -364,7 +390,17 @@ void read_state(osw_ctx* c, const DecodePlan& p, int rows, int windows, Readback
     rb.bw.resize(windows);
     HIPCHK(hipMemcpyAsync(rb.bw.data(), c->bwin, (size_t)windows * sizeof(BeamWin), hipMemcpyDeviceToHost, c->stream));
 }
-void read_tokens(osw_ctx* c, const DecodePlan& p, int rows, int windows, Readback& rb) {
+// by_row (a beam retry session with a finished sampling slot): also the rows' own tokens and
+// cumulative log-probs (rb.rtoks / rb.rcum), which a sampling slot's result is read from
+void read_tokens(osw_ctx* c, const DecodePlan& p, int rows, int windows, Readback& rb, bool by_row) {
+    if (by_row && p.beam > 1) {
+        rb.rtoks.resize((size_t)rows * p.max_tok);
+        HIPCHK(hipMemcpyAsync(rb.rtoks.data(), c->tokens, rb.rtoks.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        if (c->conf) {
+            rb.rcum.resize((size_t)rows * p.sp.lp_stride);
+            HIPCHK(hipMemcpyAsync(rb.rcum.data(), c->lp_hist, rb.rcum.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
     const size_t units = p.beam > 1 ? windows : rows;
     rb.toks.resize(units * p.max_tok);
     HIPCHK(hipMemcpyAsync(rb.toks.data(), p.beam > 1 ? c->btok : c->tokens, rb.toks.size() * 4, hipMemcpyDeviceToHost,
@@ -381,22 +417,26 @@ void read_tokens(osw_ctx* c, const DecodePlan& p, int rows, int windows, Readbac
 // Window `win`'s result, read from decoder row `row`, into r[out] and (confidences on)
 // conf_res[out].  n0 / n: the token count before / after the caller's max_tokens clamp; a row that
 // recorded n0 + 1 log-probs ended with an <|endoftext|> step, whose entry stays the last one.
+// sampled (retry sessions): the window's rows sampled, so its result is row `row`'s own whatever the
+// plan's beam (a beam session: from rb.rtoks / rb.rcum).
 void write_window(osw_ctx* c, const DecodePlan& p, osw_window_result* r, size_t out, const Readback& rb, size_t row,
-                  size_t win) {
+                  size_t win, bool sampled) {
     const SelState& q = rb.st[row];
-    const BeamWin* bw = p.beam > 1 ? &rb.bw[win] : nullptr;
+    const BeamWin* bw = p.beam > 1 && !sampled ? &rb.bw[win] : nullptr;
     const size_t unit = bw ? win : row;
+    const std::vector<int>& toks = sampled && p.beam > 1 ? rb.rtoks : rb.toks;
+    const std::vector<float>& cums = sampled && p.beam > 1 ? rb.rcum : rb.cum;
     const int n0 = bw ? bw->best_len : q.n_sampled;
     const int n = std::min(n0, std::min(p.max_tok, r->max_tokens));
     r->n_tokens[out] = n;
-    std::copy_n(&rb.toks[unit * p.max_tok], n, r->tokens + out * r->max_tokens);
+    std::copy_n(&toks[unit * p.max_tok], n, r->tokens + out * r->max_tokens);
     r->sum_logprob[out] = bw ? bw->best_raw : q.sum_lp;
     r->no_speech_prob[out] = q.nsp;
     r->language[out] = p.ss.english ? -1 : q.lang;
     if (!c->conf) return;
     if (c->conf_res.size() <= out) c->conf_res.resize(out + 1);
     osw_ctx::ConfResult& cr = c->conf_res[out];
-    const float* cum = &rb.cum[unit * p.sp.lp_stride];
+    const float* cum = &cums[unit * p.sp.lp_stride];
     const int nlp = bw ? bw->best_nlp : q.n_lp;
     cr.cum.assign(cum, cum + std::min(n, nlp));
     if (nlp == n0 + 1) cr.cum.push_back(cum[nlp - 1]);
@@ -405,17 +445,41 @@ void write_window(osw_ctx* c, const DecodePlan& p, osw_window_result* r, size_t 
 
 // After a chunk of a refill or session decode: the window slots `live` names that have finished
 // (beam: the window's stop rule, else its row), with their tokens read back into rb.
+// armed (retry sessions): armed(i) > 0 rows of slot i sample, and the slot has finished when all
+// of them have.
 std::vector<int> finished_windows(osw_ctx* c, const DecodePlan& p, int rows, int windows,
-                                  const std::function<bool(int)>& live, Readback& rb) {
+                                  const std::function<bool(int)>& live, Readback& rb,
+                                  const std::function<int(int)>& armed) {
     read_state(c, p, rows, windows, rb);
     HIPCHK(hipStreamSynchronize(c->stream));
     std::vector<int> fin;
-    for (int i = 0; i < windows; ++i)
-        if (live(i) && (p.beam > 1 ? rb.bw[i].done : rb.st[(size_t)i * p.group].done)) fin.push_back(i);
+    bool by_row = false;
+    for (int i = 0; i < windows; ++i) {
+        if (!live(i)) continue;
+        const int n = armed ? armed(i) : 0;
+        bool done = n > 0 ? true : (p.beam > 1 ? rb.bw[i].done != 0 : rb.st[(size_t)i * p.group].done != 0);
+        for (int k = 0; k < n; ++k) done = done && rb.st[(size_t)i * p.group + k].done;
+        if (!done) continue;
+        fin.push_back(i);
+        by_row = by_row || n > 0;
+    }
     if (fin.empty()) return fin;
-    read_tokens(c, p, rows, windows, rb);
+    read_tokens(c, p, rows, windows, rb, by_row);
     HIPCHK(hipStreamSynchronize(c->stream));
     return fin;
+}
+
+// best_of: of rows [first, first + n), the sample with the highest sum_logprob /
+// n_sampled**length_penalty (the first on ties)
+size_t best_sample(const Readback& rb, size_t first, int n, float length_penalty) {
+    auto norm = [&](const SelState& q) {
+        if (q.n_sampled == 0) return length_penalty != 0.f ? -INFINITY : q.sum_lp;
+        return q.sum_lp / std::pow((float)q.n_sampled, length_penalty);
+    };
+    size_t best = first;
+    for (int k = 1; k < n; ++k)
+        if (norm(rb.st[first + k]) > norm(rb.st[best])) best = first + k;
+    return best;
 }
 
 // Refill and sessions start with every row finished (nothing to step until a window is admitted)
@@ -542,21 +606,12 @@ void decode(osw_ctx* c, int nb, const osw_decode_opts* o, osw_window_result* r, 
     c->pf.decode_steps = steps;
     Readback rb;
     read_state(c, plan, rows, nb, rb);
-    read_tokens(c, plan, rows, nb, rb);
+    read_tokens(c, plan, rows, nb, rb, false);
     c->conf_res.clear();
     HIPCHK(hipStreamSynchronize(c->stream));
-    // best_of: the sample with the highest sum_logprob / n**length_penalty (first on ties)
-    auto norm = [&](const SelState& q) {
-        if (q.n_sampled == 0) return o->length_penalty != 0.f ? -INFINITY : q.sum_lp;
-        return q.sum_lp / std::pow((float)q.n_sampled, o->length_penalty);
-    };
-    for (int b = 0; b < nb; ++b) {
-        size_t best = (size_t)b * group;
-        if (plan.sampling)
-            for (int k = 1; k < group; ++k)
-                if (norm(rb.st[(size_t)b * group + k]) > norm(rb.st[best])) best = (size_t)b * group + k;
-        write_window(c, plan, r, b, rb, best, b);
-    }
+    for (int b = 0; b < nb; ++b)
+        write_window(c, plan, r, b, rb, plan.sampling ? best_sample(rb, (size_t)b * group, group, o->length_penalty)
+                                                      : (size_t)b * group, b);
     c->conf_valid = c->conf;
 }
 

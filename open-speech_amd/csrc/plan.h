@@ -62,6 +62,8 @@ struct HistRules {
 // Built once per decode call (Batch, Refill) or once per session.  n_pre: the prefix tokens before
 // <|startoftranscript|> (Batch only; sessions carry per-row prefixes in SelState::plen).
 // n_encoded > 0: a mapped decode (osw_decode_window_list) over that many encoded windows.
+// retries > 0 (Session only, osw_session_retries): the session's best_of; a slot then keeps
+// max(beam, best_of) decoder rows, so a held window can decode again there with sampling.
 struct DecodePlan {
     DecodeMode mode = DecodeMode::Batch;
     StartSeq ss;
@@ -70,12 +72,14 @@ struct DecodePlan {
     int n_pre = 0, n_encoded = 0;
     int beam = 1;   // hypotheses per window
     int group = 1;  // decoder rows per window (beam hypotheses or best_of samples)
+    int best_of = 0;  // retry sessions: sampled rows of a retried window (0: a session without retries)
     int P = 0, max_len = 0, max_tok = 0;
     SelParams sp{};
     std::vector<unsigned> mask;  // suppress_tokens as a bitmask over the vocabulary
 
     DecodePlan() = default;
-    DecodePlan(DecodeMode m, const osw_decode_opts* o, const osw_dims& d, int n_prefix = 0, int mapped_n_encoded = 0)
+    DecodePlan(DecodeMode m, const osw_decode_opts* o, const osw_dims& d, int n_prefix = 0, int mapped_n_encoded = 0,
+               int retries = 0)
         : mode(m), n_encoded(mapped_n_encoded) {
         const int V = d.n_vocab, ctx = d.n_text_ctx;
         const int wide = std::max(1, o->beam_size);
@@ -131,6 +135,7 @@ struct DecodePlan {
         s.length_penalty = o->length_penalty;
         s.lp_stride = ctx; s.lp_group = group;
         has_budget = mode == DecodeMode::Session || o->token_budget != nullptr;
+        if (retries) enable_retries(retries);
         mask.assign((V + 31) / 32, 0u);
         for (int i = 0; i < o->n_suppress; ++i) {
             const int t = o->suppress_tokens[i];
@@ -138,11 +143,25 @@ struct DecodePlan {
         }
     }
 
+    // osw_session_retries: the session keeps max(beam, best_of) rows per slot from here on
+    void enable_retries(int n) {
+        REQUIRE(mode == DecodeMode::Session, "only a decode session retries windows in place");
+        REQUIRE(n >= 1 && n <= 5, "a retry session samples 1 to 5 rows per window (best_of)");
+        best_of = n;
+        group = std::max(beam, n);
+        sp.lp_group = group;
+    }
+
     // The device side: the seed word, the per-row budgets (kept only when the call has budgets;
     // a session always has them, per window) and, with confidences on, where they are recorded
     // (all null when off, so the kernels store nothing; English-only: no language distribution).
+    // row_inv_temp / row_seed: a retry session's per-row sampling state (SelParams), else null.
     void bind(const unsigned long long* seed, const int* budget, bool conf, float* lp_hist, float* best_lp,
-              float* lang_probs) {
+              float* lang_probs, const float* row_inv_temp = nullptr, const unsigned long long* row_seed = nullptr) {
+        REQUIRE((best_of > 0) == (row_inv_temp != nullptr) && (best_of > 0) == (row_seed != nullptr),
+                "row temperatures belong to a retry session");
+        sp.row_inv_temp = row_inv_temp;
+        sp.row_seed = row_seed;
         sp.seed = seed;
         sp.budget = has_budget ? budget : nullptr;
         if (!conf) return;
@@ -155,17 +174,21 @@ struct DecodePlan {
     // The decode-graph key of CH steps over `rows` decoder rows: the mode, every scalar of
     // SelParams in declaration order (floats by their bits), then what else shapes a captured
     // launch.  The seed, the mask's contents, language tokens, prefix contents, budget values and
-    // the window map are data the launches read through fixed addresses: not in the key.
+    // the window map are data the launches read through fixed addresses: not in the key.  A retry
+    // session's launches differ (the row-temperature selection): one more word, only there, so
+    // every other key is what it was; which rows sample, at what temperature and seed is data.
     std::vector<int64_t> key(int rows, int CH) const {
-        static_assert(sizeof(SelParams) == 152, "SelParams changed: put every new scalar field into the key below");
+        static_assert(sizeof(SelParams) == 168, "SelParams changed: put every new scalar field into the key below");
         const SelParams& s = sp;
-        return {(int64_t)mode,
+        std::vector<int64_t> k{(int64_t)mode,
                 s.prompt_len, s.sot_pos, s.lang_pos, s.max_length, s.pstride, s.tail, s.sot_last, s.V, s.eot,
                 s.no_speech, s.no_ts, s.tb, s.blank, s.first_lang, s.n_langs, s.suppress_blank, s.with_ts,
                 s.max_init_ts, s.beam, s.num_hyp, s.max_cand, float_bits(s.length_penalty), float_bits(s.inv_temp),
                 s.pos_row, s.lp_stride, s.lp_group,
                 rows, group, n_pre, CH, float_bits(hr.penalty), hr.ngram, s.budget != nullptr, s.lp_hist != nullptr,
                 n_encoded};
+        if (s.row_inv_temp) k.push_back(best_of);
+        return k;
     }
 
 private:

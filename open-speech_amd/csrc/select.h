@@ -134,11 +134,14 @@ __device__ __forceinline__ SelPart load_part(const SelPart* src) {
     return r;
 }
 
-// grid (B, SEL_SPLIT), 256 threads: one vocabulary slice of one row
+// grid (B, SEL_SPLIT), 256 threads: one vocabulary slice of one row.  hrow: the Gumbel hash's
+// row argument: the row itself, or in a retry session row - slot * group, so that a retried
+// window draws what the first window of a batch decode draws with the same seed
 template <bool SAMPLE>
 __device__ __forceinline__ void select_partial_body(const float* __restrict__ logits, const SelParams& P, int step,
                                                     const unsigned* __restrict__ supmask,
-                                                    const SelState* __restrict__ st, SelPart* __restrict__ parts) {
+                                                    const SelState* __restrict__ st, SelPart* __restrict__ parts,
+                                                    const int hrow) {
     const int b = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
     const SelState s = st[b];
     const int mode = sel_mode(P, step, s);
@@ -179,7 +182,7 @@ __device__ __forceinline__ void select_partial_body(const float* __restrict__ lo
                 if (v == P.no_speech) a_text = ArgMax{xv, v};
                 if (tok_masked_w(P, R, ws[j], v)) continue;
                 lse_add(m_all, s_all, xv);
-                const float key = SAMPLE ? xv * P.inv_temp + gumbel_noise(seed, b, step, v) : xv;
+                const float key = SAMPLE ? xv * P.inv_temp + gumbel_noise(seed, hrow, step, v) : xv;
                 a_all = amax(a_all, ArgMax{key, v});
                 continue;
             }
@@ -187,7 +190,7 @@ __device__ __forceinline__ void select_partial_body(const float* __restrict__ lo
             lse_add(m_all, s_all, xv);
             // sampling: a_all / a_ts pick the Gumbel-perturbed maximum; a_text stays the plain
             // maximum (the timestamp-mass rule compares against it)
-            const float key = SAMPLE ? xv * P.inv_temp + gumbel_noise(seed, b, step, v) : xv;
+            const float key = SAMPLE ? xv * P.inv_temp + gumbel_noise(seed, hrow, step, v) : xv;
             a_all = amax(a_all, ArgMax{key, v});
             if (v >= P.tb) {
                 lse_add(m_ts, s_ts, xv);

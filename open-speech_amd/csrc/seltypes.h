@@ -43,6 +43,12 @@ struct SelParams {
     float* lang_probs;     // [windows][n_langs]: softmax over the language tokens' raw <|startoftranscript|> logits
     int lp_stride;         // floats per row of lp_hist / best_lp (n_text_ctx)
     int lp_group;          // decoder rows per window (beam_size or best_of): row w * lp_group writes lang_probs[w]
+    // Retry sessions (osw_session_retries); both nullptr otherwise.  A window slot whose first row
+    // has row_inv_temp > 0 samples: its rows with row_inv_temp > 0 draw at that 1 / temperature
+    // with their row_seed, its other rows are parked.  A slot whose first row holds 0 decodes in
+    // the session's temperature-0 mode on its first `beam` rows.
+    const float* row_inv_temp;             // [rows]
+    const unsigned long long* row_seed;    // [rows]
 };
 
 // Per window in beam mode: finished-hypothesis bookkeeping (the best one's tokens

@@ -12,6 +12,10 @@
 // their log-mel, their encoder straight into the slots' cross-K/V, then the rows' reset.
 // With osw_session_hold a finished window keeps its slot (slots.h) until osw_session_align has
 // run the word-timing pass over its cross-K/V or osw_session_release has let it go.
+// With osw_session_retries a slot keeps max(beam, best_of) rows, and osw_session_retry sends a held
+// window back to decoding in its slot with best_of sampled rows (temperature fallback), beside
+// slots that go on at temperature 0; the rows' sampling state is data the selection kernels read
+// (SelParams::row_inv_temp / row_seed), so arming a retry replays the session's decode graph.
 struct SessionWin {
     int64_t clip;            // ClipStore key (a private key < 0 for a window that brought its own PCM)
     std::vector<int> prefix;
@@ -48,6 +52,15 @@ struct Session {
     SlotTable slots;  // free / decoding / held, and the tags
     std::deque<SessionWin> queue;
     int64_t steps = 0;
+    // retry sessions (plan.best_of > 0): per slot, the admitted window's prompt (its language
+    // position as admitted: -1 for a detected language) and token budget, kept for its retries,
+    // and how many of the slot's rows sample now (0: the temperature-0 mode)
+    struct SlotWin {
+        std::vector<int> prompt;
+        int budget = 0;
+    };
+    std::vector<SlotWin> win;
+    std::vector<int> armed;
 };
 
 namespace {
@@ -179,6 +192,7 @@ void session_begin(osw_ctx* c, const osw_decode_opts* o) {
     S->W = c->B;
     bind_plan(c, S->plan, o);  // (osw_set_confidences is refused while the session is open)
     const int R = S->W * S->plan.beam;
+    c->xsplit = false;
     park_rows(c, R);
     HIPCHK(hipMemsetAsync(c->budget, 0, (size_t)R * 4, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -198,6 +212,87 @@ void session_end(osw_ctx* c) {
     c->kv_rows = 0;
     c->xkv_windows = 0;
     c->n_encoded = 0;
+    c->xsplit = false;
+}
+
+// osw_session_retries: from here on the session keeps max(beam, best_of) rows per slot and binds
+// the rows' sampling state; nothing was admitted yet, so every row is re-parked under the new
+// row count.  The buffers are the context's, allocated by its first retry session.
+void session_retries(osw_ctx* c, int best_of) {
+    Session* S = c->sess;
+    if (!S) throw OswError(OSW_ESTATE, "osw_session_retries: no decode session open");
+    if (!S->slots.hold || S->slots.added)
+        throw OswError(OSW_ESTATE, "osw_session_retries: valid after osw_session_hold(1) and before the first osw_session_add");
+    REQUIRE(best_of >= 1 && best_of <= 5, "osw_session_retries: 1 <= best_of <= 5");
+    retry_reserve(c);
+    S->plan.enable_retries(best_of);
+    const int group = S->plan.group, R = S->W * group;
+    REQUIRE(R <= c->R, "decoder rows");
+    S->plan.bind(c->seed_d, c->budget, c->conf, c->lp_hist, c->best_lp, c->lang_probs, c->row_inv_temp, c->row_seed);
+    S->win.assign(S->W, Session::SlotWin{});
+    S->armed.assign(S->W, 0);
+    std::vector<int> map(c->R);
+    for (int r = 0; r < c->R; ++r) map[r] = std::min(r / group, c->B - 1);
+    HIPCHK(hipMemcpyAsync(c->xrow_map, map.data(), map.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(c->row_inv_temp, 0, (size_t)c->R * 4, c->stream));
+    HIPCHK(hipMemsetAsync(c->row_seed, 0, (size_t)c->R * 8, c->stream));
+    park_rows(c, R);
+    HIPCHK(hipMemsetAsync(c->budget, 0, (size_t)R * 4, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->xsplit = S->plan.beam == 1 && group > 1;
+}
+
+// One pack entry of launch_session_retry_rows: `active` rows of `slot` start at step 0 of `prompt`,
+// sampling at 1 / temperature `inv_temp` with `seed` (0: the temperature-0 mode)
+void retry_pack_entry(int* e, int slot, const std::vector<int>& prompt, int budget, int active, float inv_temp,
+                      uint64_t seed) {
+    e[0] = slot;
+    e[1] = (int)prompt.size();
+    e[2] = budget;
+    e[3] = active;
+    e[4] = float_bits(inv_temp);
+    e[5] = (int)(uint32_t)seed;
+    e[6] = (int)(uint32_t)(seed >> 32);
+    e[7] = 0;
+    std::copy(prompt.begin(), prompt.end(), e + RETRY_PACK_HEAD);
+}
+
+void launch_retry_pack(osw_ctx* c, const Session* S, const std::vector<int>& pack, int k) {
+    const int ctx = c->d.n_text_ctx, beam = S->plan.beam;
+    HIPCHK(hipMemcpyAsync(c->retry_pack, pack.data(), pack.size() * 4, hipMemcpyHostToDevice, c->stream));
+    launch_session_retry_rows(c->retry_pack, k, RETRY_PACK_HEAD + ctx, S->plan.group, ctx, ctx, c->prompt, c->budget,
+                              c->cur_tok, c->pos, c->sel, beam > 1 ? c->anc : nullptr, beam > 1 ? c->bwin : nullptr,
+                              c->row_inv_temp, c->row_seed, c->stream);
+    HIPCHK(hipGetLastError());
+}
+
+// osw_session_retry: every check before any change or launch; then the slots go held -> decoding
+// and their rows are reset and armed.  The cross-K/V stays and the encoder does not run.
+void session_retry(osw_ctx* c, int n, const osw_retry_window* e) {
+    Session* S = c->sess;
+    REQUIRE(S, "no decode session open");
+    if (S->plan.best_of <= 0) throw OswError(OSW_ESTATE, "osw_session_retry: the session has no retries (osw_session_retries)");
+    REQUIRE(n >= 1 && e, "null retry argument");
+    std::vector<int64_t> tags(n);
+    for (int i = 0; i < n; ++i) {
+        REQUIRE(std::isfinite(e[i].temperature) && e[i].temperature > 0.f, "osw_session_retry: temperature must be finite and > 0");
+        REQUIRE(S->plan.ss.english || (e[i].language_token >= 0 && e[i].language_token < c->d.n_vocab),
+                "osw_session_retry: language token outside the vocabulary");
+        tags[i] = e[i].tag;
+    }
+    const std::vector<int> slots = S->slots.held_slots(n, tags.data());
+    const int ctx = c->d.n_text_ctx, ps = RETRY_PACK_HEAD + ctx;
+    std::vector<int> pack((size_t)n * ps, 0);
+    for (int i = 0; i < n; ++i) {
+        std::vector<int> prompt = S->win[slots[i]].prompt;
+        // the language attempt 0 reported (nothing is detected again)
+        if (!S->plan.ss.english) prompt[prompt.size() - S->plan.ss.tail + 1] = e[i].language_token;
+        retry_pack_entry(&pack[(size_t)i * ps], slots[i], prompt, S->win[slots[i]].budget, S->plan.best_of,
+                         1.f / e[i].temperature, e[i].seed);
+    }
+    S->slots.retry(slots);
+    for (int s : slots) S->armed[s] = S->plan.best_of;
+    launch_retry_pack(c, S, pack, n);
 }
 
 void session_add(osw_ctx* c, const int16_t* pcm, const int64_t* offsets, int n, const osw_session_window* w) {
@@ -284,6 +379,8 @@ void session_admit(osw_ctx* c, int refill_min) {
     HIPCHK(hipMemcpyAsync(c->nframes_d, c->nframes.data(), k * 4, hipMemcpyHostToDevice, c->stream));
     c->n_clips = k;
     const int ctx = c->d.n_text_ctx, beam = S->plan.beam, ps = 3 + ctx;
+    const bool retries = S->plan.best_of > 0;
+    std::vector<int> rpack(retries ? (size_t)k * (RETRY_PACK_HEAD + ctx) : 0, 0);
     std::vector<osw_window> wins(k);
     std::vector<int> slots(k), pack((size_t)k * ps, 0);
     for (int i = 0; i < k; ++i) {
@@ -298,13 +395,24 @@ void session_admit(osw_ctx* c, int refill_min) {
         e[2] = q.w.token_budget;
         for (int j = 0; j < np; ++j) e[3 + j] = q.prefix[j];
         S->plan.ss.tokens(q.w.language_token, e + 3 + np);
+        if (retries) {  // kept for the window's retries; its rows start in the temperature-0 mode
+            Session::SlotWin& sw = S->win[slot];
+            sw.prompt.assign(e + 3, e + 3 + e[1]);
+            sw.budget = q.w.token_budget;
+            S->armed[slot] = 0;
+            retry_pack_entry(&rpack[(size_t)i * (RETRY_PACK_HEAD + ctx)], slot, sw.prompt, sw.budget, beam, 0.f, 0);
+        }
     }
     encode(c, wins.data(), k, slots.data());
     for (int i = 0; i < k; ++i) S->slots.admit(free_slots[i], S->queue[i].w.tag);
-    HIPCHK(hipMemcpyAsync(c->refill_pack, pack.data(), pack.size() * 4, hipMemcpyHostToDevice, c->stream));
-    launch_session_rows(c->refill_pack, k, ps, beam, ctx, ctx, c->prompt, c->budget, c->cur_tok, c->pos, c->sel,
-                        beam > 1 ? c->anc : nullptr, beam > 1 ? c->bwin : nullptr, c->stream);
-    HIPCHK(hipGetLastError());
+    if (retries) {
+        launch_retry_pack(c, S, rpack, k);
+    } else {
+        HIPCHK(hipMemcpyAsync(c->refill_pack, pack.data(), pack.size() * 4, hipMemcpyHostToDevice, c->stream));
+        launch_session_rows(c->refill_pack, k, ps, beam, ctx, ctx, c->prompt, c->budget, c->cur_tok, c->pos, c->sel,
+                            beam > 1 ? c->anc : nullptr, beam > 1 ? c->bwin : nullptr, c->stream);
+        HIPCHK(hipGetLastError());
+    }
     for (int i = 0; i < k; ++i) {
         if (S->queue.front().clip < 0) store_release(c, S->queue.front().clip);  // (its frames were staged)
         S->queue.pop_front();
@@ -326,7 +434,8 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
         return e ? std::max(1, std::min(64, atoi(e))) : 4;
     }();
     const DecodePlan& plan = S->plan;
-    const int beam = plan.beam;
+    const int group = plan.group;  // (== beam unless the session has retries)
+    const bool retries = plan.best_of > 0;
     int done = 0;
     c->conf_res.clear();
     c->conf_valid = c->conf;
@@ -344,11 +453,17 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
         if (S->slots.decoding == 0) break;
         int hi = S->slots.decoding_end();
         if (hi > 4) hi = std::min(S->W, (hi + 3) / 4 * 4);  // (fewer graph shapes; idle slots' rows are finished)
-        const int nb = hi * beam;
+        const int nb = hi * group;
         run_chunk(c, plan, nb, hi, CH, c->use_graph && !c->prof_eager);
         S->steps += CH;
-        for (int slot : finished_windows(c, plan, nb, hi, [&](int i) { return S->slots.is_decoding(i); }, rb)) {
-            write_window(c, plan, r, done, rb, (size_t)slot * beam, slot);
+        std::function<int(int)> armed;
+        if (retries) armed = [&](int i) { return S->armed[i]; };
+        for (int slot : finished_windows(c, plan, nb, hi, [&](int i) { return S->slots.is_decoding(i); }, rb, armed)) {
+            // a sampling slot reports its best row (decode()'s best_of rule)
+            const int n_armed = retries ? S->armed[slot] : 0;
+            const size_t row = n_armed > 0 ? best_sample(rb, (size_t)slot * group, n_armed, plan.sp.length_penalty)
+                                           : (size_t)slot * group;
+            write_window(c, plan, r, done, rb, row, slot, n_armed > 0);
             tags[done] = S->slots.finish(slot);  // (hold: the slot and its cross-K/V stay)
             ++done;
         }
@@ -359,6 +474,21 @@ int session_step(osw_ctx* c, int max_chunks, int refill_min, osw_window_result* 
 }  // namespace
 
 namespace osw {
+void retry_reserve(osw_ctx* c) {
+    if (c->row_inv_temp) return;
+    const int ctx = c->d.n_text_ctx, H = c->d.n_text_head;
+    c->row_inv_temp = dalloc<float>(c->R, c->owned);
+    c->row_seed = dalloc<unsigned long long>(c->R, c->owned);
+    c->retry_pack = dalloc<int>((size_t)c->B * (RETRY_PACK_HEAD + ctx), c->owned);
+    c->xdone_single = dalloc<SelState>(c->R, c->owned);
+    c->xdone_group = dalloc<SelState>(c->R, c->owned);
+    c->xrow_map = dalloc<int>(c->R, c->owned);
+    c->xrow_ticket = dalloc<int>((size_t)c->R * H, c->owned);
+    HIPCHK(hipMemsetAsync(c->xdone_single, 0, (size_t)c->R * sizeof(SelState), c->stream));
+    HIPCHK(hipMemsetAsync(c->xdone_group, 0, (size_t)c->R * sizeof(SelState), c->stream));
+    HIPCHK(hipMemsetAsync(c->xrow_ticket, 0, (size_t)c->R * H * 4, c->stream));
+}
+
 void session_destroy(osw_ctx* c) {
     delete c->sess;
     c->sess = nullptr;
@@ -407,6 +537,24 @@ int osw_session_hold(osw_ctx* c, int32_t enable) {
         std::lock_guard<std::mutex> lk(c->mu);
         if (!c->sess) throw OswError(OSW_ESTATE, "osw_session_hold: no decode session open");
         c->sess->slots.set_hold(enable != 0);
+    });
+}
+
+int osw_session_retries(osw_ctx* c, int32_t best_of) {
+    return guard([&] {
+        REQUIRE(c, "null ctx");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        session_retries(c, best_of);
+    });
+}
+
+int osw_session_retry(osw_ctx* c, int32_t n, const osw_retry_window* entries) {
+    return guard([&] {
+        REQUIRE(c, "null ctx");
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceScope dev_scope_((c->device));
+        session_retry(c, n, entries);
     });
 }
 

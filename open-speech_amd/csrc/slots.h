@@ -6,6 +6,8 @@
 //   free --admit--> decoding --finish--> free                      (no hold)
 //                            --finish--> held --take_held--> free  (hold: osw_session_align /
 //                                                                   osw_session_release)
+//                                        held --retry--> decoding   (osw_session_retry: the window
+//                                                                   decodes again in its own slot)
 // A held slot keeps its cross-K/V: admission never picks it and finish never reports it again.
 #pragma once
 #include <cstdint>
@@ -99,6 +101,18 @@ struct SlotTable {
             state[s] = SlotState::Free;
             tag[s] = -1;
             --held;
+        }
+    }
+    // slots held_slots() returned decode again (osw_session_retry): they keep their tags and
+    // their cross-K/V, finish() holds them again
+    void retry(const std::vector<int>& slots) {
+        for (int s : slots) REQUIRE(s >= 0 && s < size() && state[s] == SlotState::Held, "slot is not held");
+        for (size_t i = 0; i < slots.size(); ++i)
+            for (size_t j = 0; j < i; ++j) REQUIRE(slots[i] != slots[j], "a slot appears twice");
+        for (int s : slots) {
+            state[s] = SlotState::Decoding;
+            --held;
+            ++decoding;
         }
     }
     // Nothing decodes, no slot is free and windows wait: a step has nothing to launch until the

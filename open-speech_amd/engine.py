@@ -418,14 +418,16 @@ class WhisperEngine:
         return self._outputs(n, bufs, dump, cfg.confidences)
 
     # ------------------------------------------------------------ decode sessions
-    def session_begin(self, cfg: DecodeConfig, hold: bool = False) -> None:
+    def session_begin(self, cfg: DecodeConfig, hold: bool = False, retries: int | None = None) -> None:
         """Open a continuous-batching decode session (osw_session_begin): windows added
         with ``session_add`` are admitted into free decoder slots between chunks of
         decoder steps, each with its own clip, seek, prefix and language.  Temperature 0
         only (greedy or beam search, beam_size <= 5); ``cfg.token_budget`` is per window
         (``session_add``), not here.  ``hold`` (osw_session_hold, word timestamps): a window
         ``session_step`` returns keeps its slot and cross-K/V until ``session_align`` or
-        ``session_release`` names its tag."""
+        ``session_release`` names its tag.  ``retries`` (osw_session_retries; needs ``hold``): the
+        ``best_of`` of the session's temperature fallback, 1 to 5; a slot then keeps
+        max(beam_size, best_of) decoder rows and ``session_retry`` decodes a held window again."""
         o, keep = self._opts(dataclasses.replace(cfg, token_budget=None), 0, None)
         self._set_confidences(cfg.confidences)  # (the session keeps the setting it begins with)
         self._sess_conf = bool(cfg.confidences)
@@ -433,6 +435,8 @@ class WhisperEngine:
         del keep
         if hold:
             self.session_hold(True)
+        if retries is not None:
+            self.session_retries(retries)
         self._sess_res = self._result(self.max_batch, 0)
         self._sess_tags = np.zeros(self.max_batch, np.int64)
 
@@ -488,6 +492,25 @@ class WhisperEngine:
         return self._align([w for _, w in windows], lambda n, arr, res: _lib.check(
             self.lib.osw_session_align(self.ctx, n, tags.ctypes.data_as(C.POINTER(C.c_int64)), arr, res),
             "osw_session_align"))
+
+    def session_retries(self, best_of: int) -> None:
+        """osw_session_retries: only in a hold-mode session before its first ``session_add``."""
+        _lib.check(self.lib.osw_session_retries(self.ctx, int(best_of)), "osw_session_retries")
+
+    def session_retry(self, entries: list) -> None:
+        """osw_session_retry: ``[(tag, temperature, seed, language_token)]`` of held windows.  Each
+        decodes again in its slot, from step 0 of the prompt it was admitted with, ``best_of``
+        rows sampling at ``temperature`` with ``seed`` (``language_token``: the language attempt 0
+        reported; None for an English-only model); ``session_step`` returns it again, held, with the
+        best row: bit for bit ``decode``'s result for the window alone at these settings."""
+        if not entries:
+            return
+        arr = (_lib.osw_retry_window * len(entries))()
+        for i, (tag, temperature, seed, lang) in enumerate(entries):
+            arr[i] = _lib.osw_retry_window(tag=int(tag), temperature=float(temperature),
+                                           seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           language_token=-1 if lang is None else int(lang))
+        _lib.check(self.lib.osw_session_retry(self.ctx, len(entries), arr), "osw_session_retry")
 
     def session_release(self, tags) -> None:
         """osw_session_release: free held windows' slots without aligning them."""
@@ -668,7 +691,8 @@ class WhisperEngine:
 
     SELECT_MODES = {"batch": 0, "refill": 1, "session": 2}
 
-    def debug_select_step(self, cfg: DecodeConfig, state: dict, mode: str = "batch", n_prefix: int = 0) -> dict:
+    def debug_select_step(self, cfg: DecodeConfig, state: dict, mode: str = "batch", n_prefix: int = 0,
+                          rows_per_slot: int | None = None, row_inv_temp=None, row_seed=None) -> dict:
         """One selection step (select kernel, and the beam update for ``cfg.beam_size`` > 1) on the
         caller's logits and state (osw_debug_select_step).  ``state`` maps the names of
         ``_lib.osw_select_io.ARRAYS`` to arrays: ``logits`` [rows][V], ``pos`` [1] or [rows],
@@ -676,7 +700,9 @@ class WhisperEngine:
         [rows][max_tok], optionally ``budget`` [rows]; beam: ``anc`` [rows][n_text_ctx], ``bwin``
         [windows] of ``BEAM_WIN``, ``best_tok`` [windows][max_tok]; with ``cfg.confidences``
         ``lp_hist``, ``best_lp``, ``lang_probs``.  Returns copies as the step left them, plus
-        ``counters`` (the context's arrival and ticket counters); the input is not changed."""
+        ``counters`` (the context's arrival and ticket counters); the input is not changed.
+        ``rows_per_slot`` with ``row_inv_temp`` / ``row_seed`` [rows] (osw_debug_select_step_rows,
+        session mode): the step of a retry session with that many rows per window slot."""
         self._set_confidences(cfg.confidences)
         cfg = dataclasses.replace(cfg, token_budget=None)
         o, keep = self._opts(cfg, 0, None)
@@ -702,7 +728,16 @@ class WhisperEngine:
         io.rows = len(out["state"])
         io.max_tok = out["tokens"].shape[1]
         io.pstride = out["prompt"].shape[1]
-        _lib.check(self.lib.osw_debug_select_step(self.ctx, C.byref(o), C.byref(io)), "osw_debug_select_step")
+        if rows_per_slot is None:
+            _lib.check(self.lib.osw_debug_select_step(self.ctx, C.byref(o), C.byref(io)), "osw_debug_select_step")
+        else:
+            rit = np.ascontiguousarray(row_inv_temp, dtype=np.float32)
+            rsd = np.ascontiguousarray(row_seed, dtype=np.uint64)
+            if len(rit) != io.rows or len(rsd) != io.rows:
+                raise ValueError("row_inv_temp / row_seed need one entry per row")
+            _lib.check(self.lib.osw_debug_select_step_rows(
+                self.ctx, C.byref(o), C.byref(io), int(rows_per_slot), rit.ctypes.data_as(C.POINTER(C.c_float)),
+                rsd.ctypes.data_as(C.POINTER(C.c_uint64))), "osw_debug_select_step_rows")
         del keep
         return out
 

@@ -44,8 +44,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .dims import check_chunk_length
-from .segments import (ClipResult, TranscribeOptions, session_supported, transcribe_clips,
-                       word_session_supported)
+from .segments import (ClipResult, TranscribeOptions, fallback_session_supported, session_supported,
+                       transcribe_clips, word_session_supported)
 from .tokenizer import WhisperTokenizer, get_suppressed_tokens
 
 
@@ -208,7 +208,7 @@ class _SessionLane(_Worker):
     the batch's longest window.  A session holds one decode configuration
     (``TranscribeOptions.key()``): a lane admits only requests of its session's key, and
     opens a session for another key once its own has drained.  Requests a session cannot
-    hold (segments.session_supported: temperature > 0 or a fallback ladder, max_new_tokens,
+    hold (a scalar temperature > 0 or a ladder that does not start at 0, max_new_tokens,
     beam_size > 5)
     run through the batched seek loop of an idle lane.
 
@@ -218,13 +218,26 @@ class _SessionLane(_Worker):
     ``session_align`` call for all the windows of a step) or released it (silence, no text, a
     failed request).  STT_HIP_WORD_SESSIONS=0 sends such requests through the batched seek
     loop instead, as does an engine without ``session_align``.
+
+    A temperature ladder (segments.fallback_session_supported: ``(0.0, 0.2, ...)``, faster-whisper's
+    ``generate_with_fallback``) rides the session as well: it is begun with ``hold`` and
+    ``retries=best_of`` (osw_session_retries), every finished window is judged by
+    ``segments.needs_fallback``, and the ones that need another temperature go back to decoding
+    in their own slots with one ``session_retry`` call per step (seed of attempt k of the clip's
+    window n: ``segments.attempt_seed(opts.seed, n, k)``, what the batched loop uses for the clip
+    alone); the others are kept by the rule of ``segments._fallback`` and then aligned or
+    released as above.  STT_HIP_FALLBACK_SESSIONS=0 sends such requests through the batched
+    seek loop instead, as does an engine without ``session_retry``.
     """
 
     def _session_ok(self, opts) -> bool:
         if session_supported(opts):
             return True
-        return (self.pool.word_sessions and word_session_supported(opts)
-                and hasattr(self.engine, "session_align"))
+        words_ok = self.pool.word_sessions and hasattr(self.engine, "session_align")
+        if fallback_session_supported(opts):
+            return (self.pool.fallback_sessions and hasattr(self.engine, "session_retry")
+                    and (words_ok or not opts.word_timestamps))
+        return words_ok and word_session_supported(opts)
 
     def _admit(self, key, room: int, idle: bool):
         """('sess', key, reqs) — requests to add to the session (key: the session's, or a
@@ -293,17 +306,20 @@ class _SessionLane(_Worker):
                 dq.cv.wait()
 
     def run(self) -> None:
-        from .segments import (align_request, apply_window, clip_state, consume_window, finish_clip, next_window,
-                               pad_alignment, plan_window, session_config)
+        from .segments import (align_request, apply_window, attempt_seed, clip_state, consume_window,
+                               fallback_verdict, finish_clip, next_window, note_language, pad_alignment, plan_window,
+                               session_config)
         pool, eng, tok = self.pool, self.engine, self.pool.tokenizer
-        flights: dict = {}      # tag -> [req, clip state, window]
+        # tag -> [req, clip state, window, windows of the clip queued so far, attempts of this window]
+        flights: dict = {}
         key, is_open, tag = None, False, 0
         added = False           # windows queued since the last admission
         words = False           # the open session holds finished windows for word timing
+        ladder = False          # the open session retries windows in place (a temperature ladder)
         held: set = set()       # tags of windows a step returned that are neither aligned nor released yet
 
         def answer(t, exc=None):
-            req, s, w = flights.pop(t)
+            req, s, w = flights.pop(t)[:3]
             if w is not None and is_open:
                 try:
                     eng.session_release_clip(t)   # the request's resident log-mel
@@ -322,7 +338,7 @@ class _SessionLane(_Worker):
                     eng.session_release([t])
 
         def queue_window(t):
-            req, s, _ = flights[t]
+            req, s = flights[t][:2]
             if s.done:
                 answer(t)
                 return
@@ -331,6 +347,8 @@ class _SessionLane(_Worker):
             # is computed once and stays on the device), later windows only the key
             w.update(tag=t, clip=t, pcm=req.pcm if flights[t][2] is None else None)
             flights[t][2] = w
+            flights[t][3] += 1
+            flights[t][4] = []
             eng.session_add([w])
             nonlocal added
             added = True
@@ -356,14 +374,17 @@ class _SessionLane(_Worker):
                 if reqs and not is_open:
                     cfg = session_config(reqs[0].opts, pool.suppress_for(reqs[0].opts))
                     words = bool(reqs[0].opts.word_timestamps)   # (one key per session: all or none)
-                    if words:
+                    ladder = len(reqs[0].opts.temperatures) > 1
+                    if ladder:
+                        eng.session_begin(cfg, hold=True, retries=int(reqs[0].opts.best_of))
+                    elif words:
                         eng.session_begin(cfg, hold=True)
                     else:
                         eng.session_begin(cfg)
                     key, is_open = k, True
                 for r in reqs:
                     tag += 1
-                    flights[tag] = [r, None, None]
+                    flights[tag] = [r, None, None, 0, []]
                     try:
                         flights[tag][1] = clip_state(0, r.pcm, r.opts, tok)
                         queue_window(tag)
@@ -386,6 +407,33 @@ class _SessionLane(_Worker):
                             self.dq.encoding -= 1
                             self.dq.cv.notify_all()
                 done, _, _ = eng.session_step(max_chunks=1, refill_min=pool.refill_min)
+                final = {}      # ladder: tag -> the window's final temperature
+                if ladder:
+                    # every window of this step is held: judge each attempt; the windows that need
+                    # the next temperature decode again in their slots (one call), the others
+                    # carry their kept result on
+                    held.update(t for t, _ in done)
+                    arm, kept = [], []
+                    for t, out in done:
+                        req, s, w, n_win, tried = flights[t]
+                        try:
+                            temps = req.opts.temperatures
+                            note_language(s, out, tok)
+                            nxt, keep = fallback_verdict(tried, out, temps, req.opts, tok)
+                            if nxt is None:
+                                final[t] = temps[len(tried) - 1]
+                                kept.append((t, keep))
+                            else:
+                                arm.append((t, temps[nxt], attempt_seed(req.opts.seed, n_win - 1, nxt),
+                                            s.lang_token if tok.special.multilingual else None))
+                        except Exception as e:  # noqa: BLE001
+                            if pool.is_device_error(e):
+                                raise
+                            answer(t, e)        # (releases the held window)
+                    if arm:
+                        eng.session_retry(arm)
+                        held.difference_update(t for t, _, _, _ in arm)
+                    done = kept
                 if words:
                     # every window of this step is held: plan each, align the ones with text in one
                     # call, release the rest, all before the next step; then keep the segments
@@ -393,9 +441,9 @@ class _SessionLane(_Worker):
                     held.update(t for t, _ in done)
                     plans, wanted = {}, []
                     for t, out in done:
-                        req, s, w = flights[t]
+                        req, s, w = flights[t][:3]
                         try:
-                            plans[t] = plan_window(s, w, out, req.opts, tok)
+                            plans[t] = plan_window(s, w, out, req.opts, tok, final.get(t))
                             aw = align_request(plans[t], w, out, req.opts, tok)
                             if aw is not None:
                                 wanted.append((t, aw))
@@ -411,13 +459,16 @@ class _SessionLane(_Worker):
                     if rest:
                         eng.session_release(rest)
                         held.difference_update(rest)
+                elif ladder and done:
+                    eng.session_release([t for t, _ in done])
+                    held.difference_update(t for t, _ in done)
                 for t, out in done:
                     if t not in flights:
                         continue
-                    req, s, w = flights[t]
+                    req, s, w = flights[t][:3]
                     try:
                         if not words:
-                            consume_window(s, w, out, req.opts, tok)
+                            consume_window(s, w, out, req.opts, tok, final.get(t))
                         elif plans[t] is not None:
                             apply_window(s, w, out, req.opts, tok, plans[t], aligned.get(t))
                         queue_window(t)
@@ -463,7 +514,7 @@ class _SessionLane(_Worker):
         # (closing: the loop above drained the flights.)  A lane marked dead because a
         # sibling lane of its GPU failed hands its unanswered requests to the surviving GPUs
         # (they restart there: a request's answer is only produced at its end)
-        for req, _, _ in flights.values():
+        for req, *_ in flights.values():
             if not req.fut.done():
                 if not self.alive:
                     pool.submit_req(req)
@@ -494,6 +545,8 @@ class BatchRunner:
         # word-timestamp requests ride the decode sessions (hold / align / release);
         # STT_HIP_WORD_SESSIONS=0: the batched seek loop of an idle lane, for A/B runs
         self.word_sessions = os.environ.get("STT_HIP_WORD_SESSIONS", "1") != "0"
+        # STT_HIP_FALLBACK_SESSIONS=0: a temperature ladder takes the batched seek loop of an idle lane
+        self.fallback_sessions = os.environ.get("STT_HIP_FALLBACK_SESSIONS", "1") != "0"
         self._sup_cache: dict = {}
         self._lock = threading.Lock()
         self.queues: list[_DevQueue] = []

@@ -321,7 +321,7 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
                         max_initial_timestamp_index=max_init, beam_size=1 if t > 0 else max(1, int(opts.beam_size)),
                         patience=opts.patience, length_penalty=opts.length_penalty, temperature=t,
                         best_of=opts.best_of,
-                        seed=(opts.seed + 0x9E3779B1 * calls + 0x85EBCA6B * k) & (2**64 - 1),
+                        seed=attempt_seed(opts.seed, calls, k),
                         repetition_penalty=float(opts.repetition_penalty),
                         no_repeat_ngram_size=int(opts.no_repeat_ngram_size), confidences=bool(opts.token_logprobs),
                         token_budget=None if budgets is None else
@@ -357,6 +357,14 @@ def transcribe_clips(engine, pcm_list: list, opts: TranscribeOptions, tok: Whisp
         code = tok.language_code(s.lang_token) if s.lang_token is not None else (opts.language or "en")
         s.result.language = code
     return [s.result for s in states]
+
+
+def attempt_seed(seed: int, call: int, k: int) -> int:
+    """The sampling seed of attempt ``k`` (the index into the temperature ladder) of chunk call
+    number ``call`` of a ``transcribe_clips`` run.  A clip transcribed alone makes one call per
+    window, so there ``call`` is the window's number in the clip (0-based, windows skipped as
+    silence included): what a session lane passes for its retries."""
+    return (int(seed) + 0x9E3779B1 * int(call) + 0x85EBCA6B * int(k)) & (2**64 - 1)
 
 
 def needs_fallback(out, avg_logprob: float, cr: float, opts: TranscribeOptions):
@@ -497,6 +505,40 @@ def word_session_supported(opts: TranscribeOptions) -> bool:
     return session_supported(dataclasses.replace(opts, word_timestamps=False))
 
 
+def fallback_session_supported(opts: TranscribeOptions) -> bool:
+    """A temperature ladder on a decode session (osw_session_retries / osw_session_retry): attempt 0
+    is the session's temperature-0 mode and a window that needs a fallback decodes again in its
+    slot with ``best_of`` sampled rows.  True for a ladder of two or more entries that starts at 0
+    and is > 0 afterwards, with 1 <= best_of <= 5, whose other options a session can hold (with or
+    without word timing).  ``session_supported`` and ``word_session_supported`` keep answering
+    False for a ladder: a driver without the retry call leaves it to the batched seek loop."""
+    temps = opts.temperatures
+    if len(temps) < 2 or temps[0] != 0 or not all(t > 0 for t in temps[1:]):
+        return False
+    if not 1 <= int(opts.best_of) <= 5:
+        return False
+    import dataclasses
+    base = dataclasses.replace(opts, temperature=0.0)
+    return session_supported(base) or word_session_supported(base)
+
+
+def fallback_verdict(tried: list, out, temps: tuple, opts: TranscribeOptions, tok: WhisperTokenizer):
+    """One attempt of a window on a session lane, by ``_fallback``'s rule: ``tried`` holds the
+    window's earlier attempts and gets this one; returns ``(retry, kept)``: the index into ``temps``
+    of the attempt to make next with ``kept`` None, or None with the result to keep (this one, or
+    when every temperature failed the best ``avg_logprob`` among those below the ratio, among all
+    without one).  The window's final temperature is ``temps[len(tried) - 1]``."""
+    avg = out.sum_logprob / (len(out.tokens) + 1)
+    needs, below = needs_fallback(out, avg, compression_ratio(tok.decode(out.tokens).strip()), opts)
+    tried.append((avg, below, out))
+    if not needs:
+        return None, out
+    if len(tried) < len(temps):
+        return len(tried), None
+    pool = [r for r in tried if r[1]] or tried
+    return None, max(pool, key=lambda r: r[0])[2]
+
+
 def session_config(opts: TranscribeOptions, suppress: tuple) -> DecodeConfig:
     """The session-wide decode configuration (transcribe_clips' per-call one, minus the
     per-window prefix, language and token budget)."""
@@ -534,14 +576,24 @@ def next_window(s: _ClipState, opts: TranscribeOptions, tok: WhisperTokenizer) -
     return dict(seek=s.seek, segment_size=size, prefix=prefix, language_token=lang, token_budget=budget)
 
 
-def consume_window(s: _ClipState, win: dict, out, opts: TranscribeOptions, tok: WhisperTokenizer) -> None:
-    _consume(s, (s.idx, win["seek"], win["segment_size"]), out, opts, tok)
+def note_language(s: _ClipState, out, tok: WhisperTokenizer) -> None:
+    """A clip whose language attempt 0 of its first window detected keeps it, with that window's
+    language probabilities (``_fallback``): a lane calls this before it retries the window."""
+    if s.lang_token is None:
+        s.lang_token = out.language
+        _set_language_probs(s.result, getattr(out, "language_probs", None), out.language, tok)
 
 
-def plan_window(s: _ClipState, win: dict, out, opts: TranscribeOptions, tok: WhisperTokenizer):
+def consume_window(s: _ClipState, win: dict, out, opts: TranscribeOptions, tok: WhisperTokenizer,
+                   temperature=None) -> None:
+    """``temperature``: the window's own final one (a fallback ladder), None: the options' scalar."""
+    _consume(s, (s.idx, win["seek"], win["segment_size"]), out, opts, tok, temperature)
+
+
+def plan_window(s: _ClipState, win: dict, out, opts: TranscribeOptions, tok: WhisperTokenizer, temperature=None):
     """``consume_window`` in two halves, for word timing on a session: the window's segments before
     they are kept (None: skipped as silence, the seek already moved), with ``text_tokens``."""
-    return _plan(s, (s.idx, win["seek"], win["segment_size"]), out, opts, tok)
+    return _plan(s, (s.idx, win["seek"], win["segment_size"]), out, opts, tok, temperature)
 
 
 def align_request(plan, win: dict, out, opts: TranscribeOptions, tok: WhisperTokenizer):
