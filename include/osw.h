@@ -791,7 +791,9 @@ int osw_debug_dec_gelu(osw_ctx* ctx, int32_t fused, int32_t M, int32_t K4, const
  * sees every byte the kernel did or did not touch (a canary; the residual of OSW_EPI_F32_RESID).
  * variant: 0 the production chooser (with the context's current CU sharing), 1 the 128 tile double
  * buffered, 2 the 256 tile, 4 the 8-phase 256 tile, 6 the 64 ring, 7 the 64 tile double buffered,
- * 11 the 128 ring, 16 the half-width 256 x 128 tile.  hi/lo operands, split-K and fragment-major
+ * 11 the 128 ring, 16 the half-width 256 x 128 tile, 20 the 8-phase tile with the fp32 epilogues'
+ * other residual prefetch depth (the kernels OSW_GEMM_RESID_PF selects), 21 the 8-phase tile on one workgroup
+ * with the next tile's first K-tile staged under each epilogue (N % 8 == 0).  hi/lo operands, split-K and fragment-major
  * weights are not offered.
  * Every precondition is checked before anything is launched (OSW_EINVAL): K % 64; lda and
  * a_grp_stride multiples of 8; every A row inside a_count elements; every C row, or the head-major

@@ -996,8 +996,9 @@ int osw_debug_enc_gemm(osw_ctx* c, const osw_enc_gemm_desc* d) {
         REQUIRE(K % 64 == 0, "GEMM K must be a multiple of 64");
         REQUIRE(epi >= EPI_F16 && epi <= EPI_HEADS, "epi: one of the six OSW_EPI_* epilogues");
         REQUIRE(variant == 0 || variant == 1 || variant == 2 || variant == 4 || variant == 6 || variant == 7 ||
-                    variant == 11 || variant == 16,
-                "variant: 0 (chooser), 1, 2, 4, 6, 7, 11 or 16");
+                    variant == 11 || variant == 16 || variant == 20 || variant == 21,
+                "variant: 0 (chooser), 1, 2, 4, 6, 7, 11, 16, 20 or 21");
+        REQUIRE((variant != 20 && variant != 21) || N % 8 == 0, "the 8-phase debug variants need N % 8 == 0");
         // A: 16-B pieces (global_load_lds), every row's K elements inside the buffer
         REQUIRE(d->lda >= 0 && d->lda <= ((int64_t)1 << 24) && d->lda % 8 == 0, "lda: a multiple of 8 elements (16 B)");
         REQUIRE(d->a_grp_rows >= 1 && d->a_grp_rows <= M, "a_grp_rows out of range");

@@ -15,6 +15,7 @@
 // im2col copy, and lets a batch of windows with padded per-window buffers be one
 // GEMM.  The C side has the same addressing.
 #include "common.h"
+#include "coresidency.h"
 #include "resln.h"
 
 #include <cstdlib>
@@ -371,6 +372,76 @@ __device__ __forceinline__ int acc_row(int wm, int mi) { return IL ? (mi >> 2) *
 template <bool IL>
 __device__ __forceinline__ int acc_col(int wn, int ni) { return IL ? (ni >> 1) * 128 + wn * 32 + (ni & 1) * 16 : wn * 64 + ni * 16; }
 
+// The thread index through an opaque move, and the wave coordinates again from it: what
+// follows shares no subexpression with the code before, so none of that code's per-thread
+// values (lane, fragment offsets, earlier addresses) stays live into it for reuse.
+__device__ __forceinline__ void fresh_tid(int& tid, int& wm, int& wn) {
+    asm volatile("" : "+v"(tid));
+    wm = tid >> 8;
+    wn = (tid >> 6) & 3;
+}
+__device__ __forceinline__ void fresh_tid(int& tid) { asm volatile("" : "+v"(tid)); }
+
+// One 128-row half (HALF, a constant: as a loop over the halves with the opaque moves in its body
+// the compiler kept the loop, picked each half's accumulators by selects and waited out every
+// piece on its own: o / fc2 at 64 windows 745 -> 1072 us, profiles/coresidency_rolled_kernel_summary.txt)
+// of the fp32 epilogues of the 8-phase kernel's budgeted forms (staged_epilogue with PF > 0, which
+// see): the half's accumulators into the LDS image, then the copy-out with PF residual /
+// positional pieces in flight.  The thread's indices are derived afresh for the image writes and
+// again for the copy-out.  Same values and the same arithmetic as staged_epilogue's loop.
+template <int EPI, int PF, int HALF>
+__device__ __forceinline__ void fp32_half_budgeted(const GemmArgs& g, const f32x4 (&acc)[8][4], int m0, int n0, float* T,
+                                                   const f32x4& b4, int tid) {
+    static_assert(EPI == EPI_F32_RESID || EPI == EPI_F32_GELU_POS, "the fused fp32 epilogues");
+    {
+        int wm, wn;
+        fresh_tid(tid, wm, wn);
+        const int lane = tid & 63;
+#pragma unroll
+        for (int mi = HALF * 4; mi < HALF * 4 + 4; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int row = acc_row<true>(wm, mi) - HALF * 128 + (lane >> 4) * 4 + i;
+                    const int col = acc_col<true>(wn, ni) + (lane & 15);
+                    T[ep32(row, col)] = acc[mi][ni][i];
+                }
+    }
+    __syncthreads();
+    fresh_tid(tid);
+#pragma unroll
+    for (int j0 = 0; j0 < 16; j0 += PF) {  // 128 rows x 64 chunks / GNT = 16 pieces per thread
+        f32x4 aux[PF];
+#pragma unroll
+        for (int jj = 0; jj < PF; ++jj) {
+            const int id = (j0 + jj) * GNT + tid;
+            const int row = id >> 6, c4 = (id & 63) * 4;
+            const int m = min(m0 + HALF * 128 + row, g.M - 1), n = min(n0 + c4, g.N - 4);
+            if constexpr (EPI == EPI_F32_RESID) aux[jj] = *(const f32x4*)((float*)g.C + c_row(g, m) + n);
+            else aux[jj] = *(const f32x4*)&g.pos[(int64_t)c_rin(g, m) * g.N + n];
+        }
+#pragma unroll
+        for (int jj = 0; jj < PF; ++jj) {
+            const int id = (j0 + jj) * GNT + tid;
+            const int row = id >> 6, c4 = (id & 63) * 4;
+            const int m = m0 + HALF * 128 + row, n = n0 + c4;
+            if (m < g.M && n < g.N) {
+                f32x4 v = *(const f32x4*)&T[ep32(row, c4)] + b4;
+                float* dst = (float*)g.C + c_row(g, m) + n;
+                if constexpr (EPI == EPI_F32_RESID) {
+                    v += aux[jj];
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]) + aux[jj][e];
+                }
+                __builtin_nontemporal_store(v, (f32x4*)dst);
+            }
+        }
+    }
+    __syncthreads();
+}
+
 // Output rows leave through nontemporal stores: the encoder's activations (0.5-2 GB per
 // GEMM at 64 windows) stream past the MALL instead of evicting the weights and the
 // next GEMM's operand panels (8p GEMMs 4-7 % and the attention after them 6 % faster).
@@ -380,10 +451,16 @@ __device__ __forceinline__ int acc_col(int wn, int ni) { return IL ? (ni >> 1) *
 // (fc1 at 64 windows 1488 -> 1432 us, + GELU 1694 -> 1627 us; profiles/r04_s_epilogue.jsonl, r04_t_epilogue_forms.jsonl)
 // TN: the tile's width (256; 128 for the half-width tile, whose waves hold accumulator
 // blocks ni < 2 only): the image keeps its 256-wide rows, the copy-out covers TN columns
-template <int EPI, bool IL = false, bool TR = false, int TN = 256>
+// PF > 0 (the production forms of the persistent 8-phase kernel, which run under the
+// co-residency budget of coresidency.h): PF residual / positional pieces in flight at once,
+// and the per-thread values re-derived at every pass instead of carried across it.
+template <int EPI, bool IL = false, bool TR = false, int TN = 256, int PF = 0>
 __device__ __forceinline__ void staged_epilogue(const GemmArgs& g, f32x4 (&acc)[8][4], int m0, int n0, int wm,
                                                 int wn, char* smem, int tid) {
     static_assert(TN == 256 || (TN == 128 && IL), "the half-width tile is the 8-phase layout");
+    static_assert(PF == 0 || (IL && (PF == 4 || PF == 8)), "the budgeted form is the 8-phase kernel's");
+    constexpr bool LEAN = PF > 0;
+    if constexpr (LEAN) fresh_tid(tid, wm, wn);
     constexpr int NI = TN / 64;        // accumulator column blocks per wave
     constexpr int C16 = TN / 8;        // 16-B fp16 chunks per image row
     constexpr int C32 = TN / 4;        // 16-B fp32 chunks per image row
@@ -442,9 +519,11 @@ __device__ __forceinline__ void staged_epilogue(const GemmArgs& g, f32x4 (&acc)[
                     T[ep16(row, col)] = (h16)epi_apply<EPI>(acc[mi][ni][i], bs[ni]);
                 }
         __syncthreads();
+        int ct = tid;  // the copy-out's thread index
+        if constexpr (LEAN) fresh_tid(ct);
 #pragma unroll 4
         for (int j = 0; j < 256 * C16 / GNT / NH; ++j) {
-            const int id = j * GNT + tid;
+            const int id = j * GNT + ct;
             const int row = half * 128 + (id >> L16), c8 = (id & (C16 - 1)) * 8;
             const int m = m0 + row, n = n0 + c8;
             if (m >= g.M || n >= g.N) continue;
@@ -467,6 +546,11 @@ __device__ __forceinline__ void staged_epilogue(const GemmArgs& g, f32x4 (&acc)[
         // this thread's 4 copy-out columns are the same in every piece (GNT % 64 == 0)
         const f32x4 b4 = hb ? *(const f32x4*)(g.bias + min(n0 + (tid & (C32 - 1)) * 4, g.N - 4))
                             : f32x4{-0.f, -0.f, -0.f, -0.f};
+        if constexpr (LEAN) {
+            fp32_half_budgeted<EPI, PF, 0>(g, acc, m0, n0, T, b4, tid);
+            fp32_half_budgeted<EPI, PF, 1>(g, acc, m0, n0, T, b4, tid);
+            return;
+        }
         for (int half = 0; half < 2; ++half) {
             if (IL || wm == half) {
 #pragma unroll
@@ -680,9 +764,11 @@ __device__ __forceinline__ void lds_sync() {  // LDS accesses of every wave done
 // in flight into ring buffer 0 (NEXT0): the image lives in buffer 1 (the upper 64 KiB) and
 // the tile leaves in passes that fit it — fp16: two 128-row halves, fp32: four 64-row
 // quarters — with LDS-only barriers, so the prefetch loads stay in flight throughout.
-template <int EPI, bool TR = false>
+// LEAN: the forms under the co-residency budget (see staged_epilogue's PF).
+template <int EPI, bool TR = false, bool LEAN = false>
 __device__ __forceinline__ void staged_epilogue_next0(const GemmArgs& g, f32x4 (&acc)[8][4], int m0, int n0, int wm,
                                                       int wn, char* smem, int tid) {
+    if constexpr (LEAN) fresh_tid(tid, wm, wn);
     const int lane = tid & 63;
     constexpr bool F16 = EPI == EPI_F16 || EPI == EPI_F16_GELU || EPI == EPI_HEADS;
     constexpr int PR = F16 ? 128 : 64;       // image rows per pass
@@ -731,9 +817,11 @@ __device__ __forceinline__ void staged_epilogue_next0(const GemmArgs& g, f32x4 (
                         T[ep16(row, col)] = (h16)epi_apply<EPI>(acc[mi][ni][i], bs[ni]);
                     }
             lds_sync();
+            int ct = tid;  // the copy-out's thread index
+            if constexpr (LEAN) fresh_tid(ct);
 #pragma unroll 4
             for (int j = 0; j < 8; ++j) {
-                const int id = j * GNT + tid;
+                const int id = j * GNT + ct;
                 const int row = id >> 5, c8 = (id & 31) * 8;
                 const int m = m0 + pass * PR + row, n = n0 + c8;
                 if (m >= g.M || n >= g.N) continue;
@@ -769,6 +857,8 @@ __device__ __forceinline__ void staged_epilogue_next0(const GemmArgs& g, f32x4 (
                         }
             }
             lds_sync();
+            int ct = tid;  // the copy-out's thread index
+            if constexpr (LEAN) fresh_tid(ct);
             // the residual (positional) operands in flight 4 at a time: every accumulator is
             // still live here (later passes), so 8 at a time spilled
 #pragma unroll
@@ -776,7 +866,7 @@ __device__ __forceinline__ void staged_epilogue_next0(const GemmArgs& g, f32x4 (
                 f32x4 aux[EPI == EPI_F32_RESID || EPI == EPI_F32_GELU_POS ? 4 : 1];
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
-                    const int id = (j0 + jj) * GNT + tid;
+                    const int id = (j0 + jj) * GNT + ct;
                     const int row = id >> 6, c4 = (id & 63) * 4;
                     const int m = min(m0 + pass * PR + row, g.M - 1), n = min(n0 + c4, g.N - 4);
                     if constexpr (EPI == EPI_F32_RESID)
@@ -786,7 +876,7 @@ __device__ __forceinline__ void staged_epilogue_next0(const GemmArgs& g, f32x4 (
                 }
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
-                    const int id = (j0 + jj) * GNT + tid;
+                    const int id = (j0 + jj) * GNT + ct;
                     const int row = id >> 6, c4 = (id & 63) * 4;
                     const int m = m0 + pass * PR + row, n = n0 + c4;
                     if (m < g.M && n < g.N) {
@@ -806,6 +896,26 @@ __device__ __forceinline__ void staged_epilogue_next0(const GemmArgs& g, f32x4 (
     }
 }
 
+// The production forms (DBG 0) of the four epilogues a 64-window encoder launches run under
+// the co-residency budget (coresidency.h).  DBG 5 and 6 are their A/B forms:
+//   5: with the NEXT0 path compiled in (OSW_GEMM_NEXT0=1), which only the GELU form takes
+//      by default: the path costs the others 3-9 VGPRs (and conv2 SGPR spills) whether it is taken or not;
+//   6: the fp32 forms with the other residual / positional prefetch depth, 4 + 8 - RESID_PF
+//      (OSW_GEMM_RESID_PF names the depth to run).
+constexpr int RESID_PF = 4;  // pieces in flight by default (4 or 8)
+template <int EPI>
+constexpr bool p8_budgeted() {
+    return EPI == EPI_F16_GELU || EPI == EPI_HEADS || EPI == EPI_F32_RESID || EPI == EPI_F32_GELU_POS;
+}
+template <int EPI, int DBG>
+constexpr bool p8_next0() {
+    return !(p8_budgeted<EPI>() && EPI != EPI_F16_GELU && (DBG == 0 || DBG == 6));
+}
+template <int EPI, int DBG>
+constexpr int p8_pf() {
+    return !p8_budgeted<EPI>() || (DBG != 0 && DBG != 5 && DBG != 6) ? 0 : DBG == 6 ? 12 - RESID_PF : RESID_PF;
+}
+
 // NEXT0: K-tile 0 of this tile was staged by the previous tile (pre0) / stage the next
 // tile's K-tile 0 (next_bid >= 0) before this tile's epilogue
 template <int EPI, int DBG>
@@ -813,10 +923,12 @@ __device__ __forceinline__ void gemm8p_tile(const GemmArgs& g, int bid, h16* sme
                                             int next_bid = -1) {
     const int wave = tid >> 6, lane = tid & 63;
     // transposed accumulators for the fp16 epilogues only: the fp32 and head-major forms
-    // need 217-219 VGPRs transposed (213-216 plain), which rounds the allocation up to 224
-    // and leaves 64 instead of 80 VGPRs per SIMD, too few for a 74-VGPR decoder
+    // needed 217-219 VGPRs transposed (213-216 plain), over ENC_GEMM_MAX_VGPRS (coresidency.h):
+    // the allocation then leaves less than CORES_DEC_MAX_VGPRS per SIMD, too few for a decoder
     // cross-attention wave of another lane to sit beside the encoder workgroup (§5.3.1)
     constexpr bool TR = DBG != 2 && (EPI == EPI_F16 || EPI == EPI_F16_GELU);
+    constexpr bool NX = p8_next0<EPI, DBG>();
+    constexpr int PF = p8_pf<EPI, DBG>();
     int m0, n0;
     tile8p_origin(g, bid, m0, n0);
 
@@ -1013,7 +1125,7 @@ __device__ __forceinline__ void gemm8p_tile(const GemmArgs& g, int bid, h16* sme
     }
     }
     if (__builtin_amdgcn_readfirstlane(wave) < 4) barrier();
-    if (next_bid >= 0) {
+    if (NX && next_bid >= 0) {
         // every wave is past its reads of buffer 0 (the last K-tile read buffer 1: nk even):
         // the next tile's K-tile 0 streams in while this tile's epilogue runs in buffer 1
         lds_sync();
@@ -1027,7 +1139,7 @@ __device__ __forceinline__ void gemm8p_tile(const GemmArgs& g, int bid, h16* sme
             for (int i = 0; i < 2; ++i)
                 __builtin_amdgcn_global_load_lds((const void*)src8p(g, nm0, nn0, H, i, wave, lane),
                                                  (OSW_LDS void*)(smem + H * HT + (i * 8 + wave) * 8 * BK), 16, 0, 0);
-        if constexpr (!NOEPI) staged_epilogue_next0<EPI, TR>(g, acc, m0, n0, wm, wn, (char*)smem, tid);
+        if constexpr (!NOEPI) staged_epilogue_next0<EPI, TR, (PF > 0)>(g, acc, m0, n0, wm, wn, (char*)smem, tid);
         return;
     }
     if constexpr (NOEPI) {
@@ -1038,7 +1150,7 @@ __device__ __forceinline__ void gemm8p_tile(const GemmArgs& g, int bid, h16* sme
             for (int j = 0; j < 4; ++j) t += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
         if (t == 1234.5f) ((float*)g.C)[tid] = t;  // keeps the loop live
     } else {
-        staged_epilogue<EPI, true, TR>(g, acc, m0, n0, wm, wn, (char*)smem, tid);
+        staged_epilogue<EPI, true, TR, 256, PF>(g, acc, m0, n0, wm, wn, (char*)smem, tid);
     }
 }
 
@@ -1048,17 +1160,20 @@ __device__ __forceinline__ void gemm8p_tile(const GemmArgs& g, int bid, h16* sme
 // one-tile-per-workgroup grid).  No encoder
 // workgroups then wait in the dispatcher, where they delayed another lane's decoder
 // dispatches by 17-30 us each; every decoder kernel of a greedy step must
-// then fit beside an encoder workgroup (<= 30 KiB of LDS, <= 80 VGPRs); the 64-row logits
-// GEMM (80 KiB) does not.  4832 vs 4789 audio-s/s (12 steps, two runs each).
+// then fit beside an encoder workgroup (coresidency.h: CORES_DEC_MAX_LDS, CORES_DEC_MAX_VGPRS,
+// and this kernel's production forms within ENC_GEMM_MAX_VGPRS; tests/test_kernel_resources_cpu.py
+// holds the build to it); the 64-row logits GEMM (128 KiB) does not.  4832 vs 4789 audio-s/s
+// (12 steps, two runs each).
 // DBG (debug variants): 1 no epilogue (9: main-loop time alone), 2 the accumulators not
-// transposed (the round-3 fp16 epilogues; 12, 13)
+// transposed (the round-3 fp16 epilogues; 12, 13), 5 / 6 the A/B forms of the budgeted epilogues
+// (p8_next0, p8_pf)
 template <int EPI, int DBG = 0>
 __global__ __launch_bounds__(GNT, 1) void gemm8p_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) h16 smem[];  // [2][A0 A1 W0 W1][128*64]
     const int nwg = ((g.N + GB - 1) / GB) * ((g.M + GB - 1) / GB);
     // next0 (g.kc bit, see launch8p): the next tile's first K-tile is staged before this
     // tile's epilogue (needs an even K-tile count: the last K-tile then sits in buffer 1)
-    const bool next0 = g.kc == 1 && (g.K / BK) % 2 == 0;
+    const bool next0 = p8_next0<EPI, DBG>() && g.kc == 1 && (g.K / BK) % 2 == 0;
     bool pre0 = false;
     for (int vb = blockIdx.x; vb < nwg; vb += gridDim.x) {
         // the thread id passes through an opaque move each tile, so nothing derived from it
@@ -1097,8 +1212,21 @@ int grid8(const GemmArgs& g) {
     return per_tile ? 1 << 30 : std::max(8, g.share_cus ? shared_cap : cus);
 }
 
+// OSW_GEMM_RESID_PF=4 | 8: the fp32 epilogues' residual / positional prefetch depth (default
+// RESID_PF); one library serves both, so they can be A/B'd on one box.
+int resid_pf() {
+    static const int pf = [] {
+        const char* e = std::getenv("OSW_GEMM_RESID_PF");
+        const int v = e ? atoi(e) : RESID_PF;
+        return v == 4 || v == 8 ? v : RESID_PF;
+    }();
+    return pf;
+}
+
+// force (debug variants 20, 21): 1 the other prefetch depth's form, 2 the NEXT0 path on ONE workgroup
+// (every tile but the last then leaves through staged_epilogue_next0, at any tile count)
 template <int EPI, int DBG = 0>
-void launch8p(const GemmArgs& g0, hipStream_t s) {
+void launch8p(const GemmArgs& g0, hipStream_t s, int force = 0) {
     constexpr int lds = EPI_LDS > 8 * HT * 2 ? EPI_LDS : 8 * HT * 2;
     set_lds_once((const void*)gemm8p_kernel<EPI, DBG>, lds);
     GemmArgs g = g0;
@@ -1113,10 +1241,26 @@ void launch8p(const GemmArgs& g0, hipStream_t s) {
         const char* e = std::getenv("OSW_GEMM_NEXT0");
         return e ? (e[0] == '1' ? 1 : 0) : -1;
     }();
-    const bool next0 = next0_env < 0 ? EPI == EPI_F16_GELU : next0_env == 1;
+    const bool next0 = force == 2 || (next0_env < 0 ? EPI == EPI_F16_GELU : next0_env == 1);
     g.kc = next0 ? 1 : 0;  // (kc is unused by the 8-phase kernel otherwise)
     const int nwg = ((g.N + GB - 1) / GB) * ((g.M + GB - 1) / GB);
-    gemm8p_kernel<EPI, DBG><<<std::min(nwg, grid8(g)), GNT, lds, s>>>(g);
+    const int grid = force == 2 ? 1 : std::min(nwg, grid8(g));
+    // the production forms whose NEXT0 path or deeper prefetch lives in an A/B form (p8_next0, p8_pf)
+    if constexpr (DBG == 0 && !p8_next0<EPI, 0>()) {
+        if (next0) {
+            set_lds_once((const void*)gemm8p_kernel<EPI, 5>, lds);
+            gemm8p_kernel<EPI, 5><<<grid, GNT, lds, s>>>(g);
+            return;
+        }
+    }
+    if constexpr (DBG == 0 && (EPI == EPI_F32_RESID || EPI == EPI_F32_GELU_POS)) {
+        if (force == 1 || resid_pf() != RESID_PF) {
+            set_lds_once((const void*)gemm8p_kernel<EPI, 6>, lds);
+            gemm8p_kernel<EPI, 6><<<grid, GNT, lds, s>>>(g);
+            return;
+        }
+    }
+    gemm8p_kernel<EPI, DBG><<<grid, GNT, lds, s>>>(g);
 }
 
 // Half-width tile (256 x 128 x 64) for the encoder at one to a few windows, where the 256²
@@ -2583,6 +2727,11 @@ void prepare_gemm_kernels() {
         set_lds_once((const void*)gemm8h_kernel<EPI_F32, 1>, H8_LDS);
         set_lds_once((const void*)gemm8p_kernel<EPI_F16, 2>, l8p);
         set_lds_once((const void*)gemm8p_kernel<EPI_F16_GELU, 2>, l8p);
+        set_lds_once((const void*)gemm8p_kernel<EPI_HEADS, 5>, l8p);
+        set_lds_once((const void*)gemm8p_kernel<EPI_F32_RESID, 5>, l8p);
+        set_lds_once((const void*)gemm8p_kernel<EPI_F32_GELU_POS, 5>, l8p);
+        set_lds_once((const void*)gemm8p_kernel<EPI_F32_RESID, 6>, l8p);
+        set_lds_once((const void*)gemm8p_kernel<EPI_F32_GELU_POS, 6>, l8p);
         set_lds_once((const void*)gemm_wide_kernel<true, 256>, wide_lds<256>(true));
         set_lds_once((const void*)gemm_wide_kernel<false, 256>, wide_lds<256>(false));
         set_lds_once((const void*)gemm_wide_kernel<true, 256, true>, wide_lds<256>(true));
@@ -2673,18 +2822,21 @@ void launch_gemm_variant(const GemmArgs& g, int variant, hipStream_t s) {
         else launch8p<EPI_F16_GELU, 2>(g, s);
         return;
     }
-    if (variant == 4 || (variant == 0 && big && !two_phase)) {
+    // debug: the 8-phase tile with the fp32 epilogues' other prefetch depth (20) / the NEXT0 path on one workgroup (21)
+    const int force8p = variant == 20 ? 1 : variant == 21 ? 2 : 0;
+    if (force8p && (g.A_lo || g.N % 8 != 0)) throw std::invalid_argument("the 8-phase debug variants need fp16 A and N % 8 == 0");
+    if (force8p || variant == 4 || (variant == 0 && big && !two_phase)) {
         static const bool plain = [] {  // OSW_GEMM_TR=0: fp16 epilogues without transposed accumulators (A/B)
             const char* e = std::getenv("OSW_GEMM_TR");
             return e && e[0] == '0';
         }();
         switch (g.epi) {
-            case EPI_F16: plain ? launch8p<EPI_F16, 2>(g, s) : launch8p<EPI_F16>(g, s); return;
-            case EPI_F16_GELU: plain ? launch8p<EPI_F16_GELU, 2>(g, s) : launch8p<EPI_F16_GELU>(g, s); return;
-            case EPI_F32_RESID: launch8p<EPI_F32_RESID>(g, s); return;
-            case EPI_F32_GELU_POS: launch8p<EPI_F32_GELU_POS>(g, s); return;
-            case EPI_F32: launch8p<EPI_F32>(g, s); return;
-            default: launch8p<EPI_HEADS>(g, s); return;
+            case EPI_F16: plain ? launch8p<EPI_F16, 2>(g, s, force8p) : launch8p<EPI_F16>(g, s, force8p); return;
+            case EPI_F16_GELU: plain ? launch8p<EPI_F16_GELU, 2>(g, s, force8p) : launch8p<EPI_F16_GELU>(g, s, force8p); return;
+            case EPI_F32_RESID: launch8p<EPI_F32_RESID>(g, s, force8p); return;
+            case EPI_F32_GELU_POS: launch8p<EPI_F32_GELU_POS>(g, s, force8p); return;
+            case EPI_F32: launch8p<EPI_F32>(g, s, force8p); return;
+            default: launch8p<EPI_HEADS>(g, s, force8p); return;
         }
     }
     if (big) {

@@ -11,7 +11,7 @@ import csv
 import gzip
 import sys
 
-ENC = ("gemm8p", "enc_attn", "layernorm_kernel", "mel_", "gemm_kernel", "gemm64_ring")
+ENC = ("gemm8p", "gemm8h", "enc_attn", "layernorm_kernel", "layernorm4_kernel", "mel_", "gemm_kernel", "gemm64_ring")
 
 
 def load(path):
